@@ -1,6 +1,14 @@
 """Benchmark of the detection-output hot path (BASELINE.json metric, configs[1] / configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model ssd|frcnn|both] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--model ssd|frcnn|both]
+
+A plain run sets up the SSDLite workload, warms up, times the K steps and prints the JSON line (metric,
+value, unit, higher_is_better, dtype, ms_per_step, the workload's config and how the steps were timed).
+--dump-outputs DIR then writes the detections the timed path delivered (dump_outputs).  Everything else
+the benchmark measures is behind --full: FRCNN beside SSDLite (--model defaults to both there), the
+roofline of the dominant kernel, the SSD rate at the other in-flight count, the end-to-end rates, the
+CPU baselines and the ORIE comparison against the CPU oracle; --no-roofline / --no-alt / --no-e2e /
+--no-cpu take single legs out of a --full run.
 
 A step = one forward of the detector over one batch of synthetic 640x640 images already resident in
 HBM as the decoded uint8 images the detect CLI hands the engine (read_image's output, detect.py:57; the
@@ -76,6 +84,7 @@ def step(plan, stream, d2h):
 
 
 TIMING = {}  # how the last timed_steps call measured (reported on the JSON line)
+LANES = []   # the last timed_steps call's instances: (plan, stream, pinned D2H buffers) (dump_outputs)
 SETTLE_S = float(os.environ.get("EDGEDET_BENCH_SETTLE", "0.5"))  # untimed device warm-up before the warmup passes (s)
 
 
@@ -109,6 +118,7 @@ def timed_steps(plan, stream, steps, warmup, dist, extra=()):
     its start).  The host wall clock of the K timed passes (from the first timed issue to the last timed
     pass's completion) is kept in TIMING."""
     lanes = [(p, s, d2h_buffers(p)) for p, s in [(plan, stream)] + list(extra)]
+    LANES[:] = lanes
     n = len(lanes)
     warm = max(warmup, n)
     torch.cuda.synchronize()
@@ -179,6 +189,32 @@ def timed_steps(plan, stream, steps, warmup, dist, extra=()):
                    "device_s": round(el, 6), "interval_passes": steps + r, "wall_s": round(wall, 6),
                    "warmup_passes": warm, "settle_passes": settled, "instances": n})
     return el
+
+
+def dump_outputs(out_dir, model):
+    """Write what the timed path delivered, the pinned host arrays of the detections, as float32
+    out_dir/<model>_i<k>_{count,boxes,scores,labels}.npy for each instance k the steps rotated over:
+    count [B], boxes [B,K,4], scores [B,K], labels [B,K], rows at and past an image's count zeroed
+    (a caller receives rows [:count]; the padding is whatever the arena held).  An instance's input
+    is fixed by its seed and every pass of an instance recomputes the same batch, so its buffers hold
+    its last pass.  Which instance the last timed step fell on depends on how many settle passes fitted
+    into the settle time, so all of them are written: the files are the same set from run to run.
+    Called after timed_steps has drained the streams; releases the instances it kept (LANES)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (_, _, d2h) in enumerate(LANES):
+        count, boxes, scores, labels = (host.numpy() for _, host in d2h)
+        keep = np.arange(boxes.shape[1])[None, :] < count.reshape(-1, 1)
+        arrays = {"count": count, "boxes": np.where(keep[:, :, None], boxes, 0),
+                  "scores": np.where(keep, scores, 0), "labels": np.where(keep, labels, 0)}
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{model}_i{k}_{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def release_lanes(dump_dir, rank, model):
+    """After a model's timed steps: write its outputs if asked (rank 0), let its instances go."""
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, model)
+    LANES.clear()
 
 
 def end_to_end(m, B, batches, seed):
@@ -775,7 +811,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=750)  # about 1 s of timed SSD work
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--model", default="both", choices=["ssd", "frcnn", "retinanet", "both", "all"])
+    ap.add_argument("--model", default=None, choices=["ssd", "frcnn", "retinanet", "both", "all"],
+                    help="default: ssd, the headline workload; both with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: FRCNN beside SSDLite, the roofline, "
+                         "the other in-flight count, the end-to-end rates, the CPU baselines and the ORIE comparison")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the detections the timed path delivered to DIR/<name>.npy "
+                         "(float32; dump_outputs)")
     ap.add_argument("--retina-batch", type=int, default=8)
     ap.add_argument("--ssd-batch", type=int, default=32)
     ap.add_argument("--frcnn-batch", type=int, default=8)
@@ -796,6 +839,12 @@ def main():
                          "engine input; /255 in the device transform, bit-identical to the host's float path) "
                          "or the model contract's float images")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps of the headline workload and nothing else
+        if args.dump_ops:
+            ap.error("--dump-ops takes the per-op times of the roofline leg: it needs --full")
+        args.no_roofline = args.no_alt = args.no_e2e = args.no_cpu = True
+    if args.model is None:
+        args.model = "both" if args.full else "ssd"
     u8 = args.input == "u8"
     # EDGEDET_DIAG_SKIP (honoured only by a -DEDGEDET_DIAG build, libedgedet_diag.so) leaves op families
     # out: wrong results, so a measurement under it is never a product number
@@ -821,6 +870,7 @@ def main():
         nin = args.inflight or m.INFLIGHT
         extra = inflight_instances(m, B, nin, 100 * rank, u8)
         el = timed_steps(plan, stream, args.steps, args.warmup, dist, extra)
+        release_lanes(args.dump_outputs, rank, "ssd")
         out["ssd"] = {"value": world * B * args.steps / el, "ms_per_step": 1e3 * el / args.steps, "batch": B,
                       "inflight": nin, "dets_per_img": float(plan.out_count.tensor().float().mean().item()),
                       "timing": dict(TIMING)}
@@ -838,6 +888,7 @@ def main():
             alt = 2 if nin != 2 else 4
             more = inflight_instances(m, B, alt - nin + 1, 100 * rank + 7, u8) if alt > nin else []
             el2 = timed_steps(plan, stream, args.steps, args.warmup, dist, (extra + more)[:alt - 1])
+            LANES.clear()
             del more
             out["ssd"]["alt_inflight"] = {"inflight": alt, "value": round(world * B * args.steps / el2, 2)}
         del extra
@@ -861,6 +912,7 @@ def main():
         steps = max(20, args.steps // 10)
         extra = inflight_instances(m, B, args.inflight or m.INFLIGHT, 100 * rank + 70, u8)
         el = timed_steps(plan, stream, steps, max(2, args.warmup // 4), dist, extra)
+        release_lanes(args.dump_outputs, rank, "retinanet")
         out["retinanet"] = {"value": world * B * steps / el, "ms_per_step": 1e3 * el / steps, "batch": B,
                             "dets_per_img": float(plan.out_count.tensor().float().mean().item())}
         if rank == 0 and not args.no_roofline:
@@ -882,6 +934,7 @@ def main():
         extra = inflight_instances(m, B, args.inflight or m.INFLIGHT, 100 * rank + 50, u8)
         steps = max(20, args.steps // 10)  # FRCNN steps are ~20x SSD's: at least 20 (about half a second)
         el = timed_steps(plan, stream, steps, max(2, args.warmup // 4), dist, extra)
+        release_lanes(args.dump_outputs, rank, "frcnn")
         timing = dict(TIMING)
         R = float(plan.proposal_count.tensor().float().mean().item())
         gflop = 2 * (151.45e9 + 128.92e6 * R) / 1e9

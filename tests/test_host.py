@@ -340,3 +340,38 @@ def test_bench_attaches_committed_pmc_traffic():
                  {"launch": base + "#0", "grid_wg": pmc["grid_wg"], "traffic": None, "kernel": "other_kernel"}):
         bench.attach_traffic(roof, "ssd")
         assert roof["traffic"] is None
+
+
+def test_bench_dump_outputs_writes_what_a_caller_receives(tmp_path):
+    """bench.dump_outputs: one float32 .npy per output array and in-flight instance, rows [:count] of
+    each image as delivered, the padding past them zeroed (it is whatever the arena held)."""
+    import importlib.util
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    lanes, want = [], []
+    for k in range(2):
+        count = torch.tensor([0, 2, 5], dtype=torch.int32)
+        boxes = torch.rand((3, 5, 4), generator=g) + 1
+        scores = torch.rand((3, 5), generator=g) + 1
+        labels = torch.randint(1, 91, (3, 5), generator=g)
+        lanes.append((None, None, [(None, t) for t in (count, boxes, scores, labels)]))
+        want.append((count, boxes, scores, labels))
+    bench.LANES[:] = lanes
+    bench.release_lanes(str(tmp_path), 0, "ssd")
+    assert bench.LANES == []
+    assert sorted(os.listdir(tmp_path)) == sorted(f"ssd_i{k}_{n}.npy" for k in range(2)
+                                                  for n in ("count", "boxes", "scores", "labels"))
+    for k, (count, boxes, scores, labels) in enumerate(want):
+        got = {n: np.load(tmp_path / f"ssd_i{k}_{n}.npy") for n in ("count", "boxes", "scores", "labels")}
+        assert all(a.dtype == np.float32 for a in got.values())
+        assert got["count"].tolist() == [0, 2, 5]
+        for b, c in enumerate(count.tolist()):
+            assert np.array_equal(got["boxes"][b, :c], boxes[b, :c].numpy()) and not got["boxes"][b, c:].any()
+            assert np.array_equal(got["scores"][b, :c], scores[b, :c].numpy()) and not got["scores"][b, c:].any()
+            assert np.array_equal(got["labels"][b, :c], labels[b, :c].numpy()) and not got["labels"][b, c:].any()
+    bench.release_lanes("", 0, "ssd")  # nothing asked for: nothing written, no error

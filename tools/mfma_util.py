@@ -1,7 +1,7 @@
 """MFMA utilisation of the conv kernels from one rocprofv3 PMC pass.
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d <dir> -o m -- \
-        python3 bench.py --model frcnn --steps 2 --warmup 1 --no-cpu --no-roofline --inflight 1
+        python3 bench.py --full --model frcnn --steps 2 --warmup 1 --no-cpu --no-roofline --inflight 1
     python tools/mfma_util.py <dir> [--model frcnn]
 
 Per dispatch (MI355X_MICROARCH.md, "s_memtime tick vs SQ PMC units"):
