@@ -312,18 +312,24 @@ def test_batched_nms_matches_oracle():
     np.testing.assert_array_equal(got, ref)
 
 
-def test_roi_align_matches_oracle():
+@pytest.mark.parametrize("C", [32, 4])
+@pytest.mark.parametrize("sampling_ratio", [2, 0])
+def test_roi_align_matches_oracle(sampling_ratio, C):
+    """sampling_ratio 0 is the adaptive grid: ceil(roi / PH) samples per bin, in the C reference and
+    in the kernel alike."""
     from edgeml_amd import ops
     from oracle import tv_ops
     rs = np.random.RandomState(6)
-    B, C, H, W = 2, 32, 25, 31
+    B, H, W = 2, 25, 31
     feat = torch.from_numpy(rs.randn(B, C, H, W).astype(np.float32))
     R = 64
     bx = _rand_boxes(rs, R, 120.0)
     bx[:4] = [[-10, -10, 5, 5], [0, 0, 1, 1], [100, 90, 130, 140], [50, 50, 50.5, 50.2]]
+    bx[4] = [2, 1, 122, 99]  # 30 x 24.5 feature pixels: an adaptive grid of 5 x 4 samples per bin
     rois = np.concatenate([rs.randint(0, B, (R, 1)).astype(np.float32), bx], 1).astype(np.float32)
-    ref = tv_ops.roi_align(feat, rois, 0.25)
-    got = ops.roi_align_nhwc(feat.permute(0, 2, 3, 1).contiguous().to(DEV), torch.from_numpy(rois).to(DEV), 0.25)
+    ref = tv_ops.roi_align(feat, rois, 0.25, sampling_ratio=sampling_ratio)
+    got = ops.roi_align_nhwc(feat.permute(0, 2, 3, 1).contiguous().to(DEV), torch.from_numpy(rois).to(DEV), 0.25,
+                             sampling_ratio=sampling_ratio)
     got = got.permute(0, 3, 1, 2).cpu()
     assert torch.equal(got, ref), (got - ref).abs().max().item()
 
@@ -356,8 +362,9 @@ def test_split_bf16x3_device_matches_host():
     assert np.array_equal(got, split_bf16x3(w.numpy()))
 
 
-@pytest.mark.parametrize("tile", [0, 22, 23, 24, 25, 27, 28, 29, 30, 31, 32, 38, 39])
-@pytest.mark.parametrize("case", [CONV_CASES[i] for i in (0, 1, 2, 3, 4, 5, 7, 8)])
+@pytest.mark.parametrize("tile", [0, 21, 22, 23, 24, 25, 27, 28, 29, 30, 31, 32, 38, 39])
+@pytest.mark.parametrize("case", [CONV_CASES[i] for i in (0, 1, 2, 3, 4, 5, 7, 8)] +
+                         [(1, 13, 11, 256, 36, 3, 1, None, False)])  # the RPN head 3x3 class (tile 21's layer)
 def test_conv_bf16x6_matches_torch(case, tile):
     _conv_case(*case, tile=tile, x6=True)
 
@@ -409,7 +416,7 @@ def test_conv_bf16x6_split_k(case):
     assert torch.equal(y1, y2)
 
 
-@pytest.mark.parametrize("tile", [25, 29, 30, 31, 32, 38, 39])
+@pytest.mark.parametrize("tile", [21, 25, 29, 30, 31, 32, 38, 39])
 @pytest.mark.parametrize("se", [False, True])
 @pytest.mark.parametrize("case", [(2, 9, 9, 16, 16, 1, 1, None, True), (3, 11, 7, 24, 72, 1, 1, "HS", False),
                                   (2, 13, 10, 40, 120, 1, 1, "RE", False), (1, 20, 20, 72, 24, 1, 1, None, True)])
@@ -420,7 +427,7 @@ def test_conv_bf16x6_pointwise_ragged_cin(case, se, tile):
     _conv_case(*case, tile=tile, se=se, x6=True)
 
 
-@pytest.mark.parametrize("tile", [22, 23, 24, 25, 29, 30, 31, 32, 38, 39])
+@pytest.mark.parametrize("tile", [21, 22, 23, 24, 25, 29, 30, 31, 32, 38, 39])
 def test_conv_bf16x6_se_scale(tile):
     _conv_case(2, 10, 10, 480, 160, 1, 1, None, True, tile=tile, se=True, x6=True)
 
