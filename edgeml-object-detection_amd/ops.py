@@ -52,6 +52,8 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_split_bf16x3", "edgedet_conv_tile", "edgedet_box_correct", "edgedet_orie_ap",
            "edgedet_map_eval", "edgedet_output_features", "edgedet_conv2d_x3", "edgedet_ssd_stem",
            "edgedet_mlp_state_size", "edgedet_mlp_fit", "edgedet_mlp_predict",
+           "edgedet_dcsb_fit", "edgedet_svm_workspace_size", "edgedet_svm_fit", "edgedet_svm_hessian",
+           "edgedet_svm_decision",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
            "edgedet_model_prepare_host", "edgedet_model_forward", "edgedet_model_max_detections",
            "edgedet_model_records", "edgedet_ssdlite_workspace_size", "edgedet_ssdlite_forward",
@@ -126,6 +128,16 @@ def lib():
                                   _vp, _i32, _i32, ctypes.c_float, ctypes.c_float, _vp, _i32, ctypes.c_float, _i32,
                                   ctypes.c_float, ctypes.c_uint64, _vp]
     L.edgedet_mlp_predict.argtypes = [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]
+    L.edgedet_dcsb_fit.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]
+    L.edgedet_svm_workspace_size.argtypes = [_i32, _i64, _i64]
+    L.edgedet_svm_workspace_size.restype = _i64
+    L.edgedet_svm_fit.argtypes = [_vp, _i64, _i64, _vp, _dbl, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _dbl, _vp,
+                                  _vp, _vp, _vp]
+    L.edgedet_svm_hessian.argtypes = [_vp, _i64, _vp, _i64, _vp, _vp, _vp]
+    L.edgedet_svm_decision.argtypes = [_vp, _i64, _i64, _vp, _i32, _vp, _vp]
+    for name in ("edgedet_dcsb_fit", "edgedet_svm_fit", "edgedet_svm_hessian", "edgedet_svm_decision"):
+        getattr(L, name).restype = ctypes.c_int
     _u64 = ctypes.c_uint64
     L.edgedet_model_weights_size.argtypes = [_i32, _i32, _i32]
     L.edgedet_model_weights_size.restype = _i64

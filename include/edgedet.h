@@ -370,6 +370,47 @@ int edgedet_map_eval(const int32_t* ent_img, const uint8_t* ent_flag, const int6
 int edgedet_output_features(const double* rows, const int64_t* off, int64_t n_img, int32_t ncol, int32_t num_class,
                             int32_t k, double* out, void* stream);
 
+/* ------------------------------------------------------------------ comparison baselines (baseline.py) */
+/*
+ * baseline.py:67-152 fit_dcsb for every cross-validation fold in one launch (a workgroup per fold),
+ * bit-exact: float64 and integer arithmetic only.  conf / area [n_det] are every image's detections
+ * (grouped by det_off [N + 1]); fold f trains on images tr_idx[tr_off[f] .. tr_off[f+1]); label_num [N]
+ * labels per image; reward [N] 0 / 1; grid [n_grid <= 128] the area thresholds (np.arange(0.2, 0.9, 0.01),
+ * computed by the caller).  Scratch: ws_num [F][2][N] int32, ws_area [F][N].  Writes per fold
+ * thresh = (conf_thresh, area_thresh), num_thresh, est [F][N] (the estimate of every image, training and
+ * validation), steps (bisection halvings) and status: 0 ok, 1 the confidence bisection did not meet
+ * the reference's stopping rule within 64 halvings (the reference loops forever there), 2 no grid
+ * cell has a positive accuracy.
+ */
+int edgedet_dcsb_fit(const double* conf, const double* area, const int64_t* det_off, int64_t N,
+                     const int64_t* label_num, const int32_t* reward, const int32_t* tr_idx, const int64_t* tr_off,
+                     int32_t folds, const double* grid, int32_t n_grid, int32_t* ws_num, double* ws_area,
+                     double* thresh, int32_t* num_thresh, int32_t* est, int32_t* status, int32_t* steps,
+                     void* stream);
+/*
+ * baseline.py:29-64 fit_af: the optimum of LinearSVC(dual=False, class_weight={0: 1, 1: pos_weight}),
+ * f(v) = 1/2 |v|^2 + sum_i C_i max(0, 1 - s_i v.x_i)^2, per fold by a damped Newton method in float64
+ * (Hessian by the fp64 matrix instruction, Cholesky, Armijo line search).  x [N][Dp]: the features, a
+ * column of ones (the regularised bias) and zero columns up to Dp, a multiple of 16, <= 256; y [N]
+ * 0 / 1; tr_off_host is the host copy of the device array tr_off [F + 1].  v [F][Dp] holds the start
+ * (zeros) and receives the solution; ws: edgedet_svm_workspace_size bytes, total_rows = tr_off[F].
+ * Stops a fold at |grad f| <= tol or after max_iter Newton steps; writes iters, gnorm (the last
+ * gradient norm) and status (0 ok, 1 not converged, 2 line search failed, 3 Hessian not positive
+ * definite) per fold.  Synchronises the stream: the iteration count is decided on the device.
+ */
+int64_t edgedet_svm_workspace_size(int32_t folds, int64_t Dp, int64_t total_rows);
+int edgedet_svm_fit(const double* x, int64_t N, int64_t Dp, const int32_t* y, double pos_weight,
+                    const int32_t* tr_idx, const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, double* v,
+                    void* ws, int64_t ws_bytes, int32_t max_iter, double tol, int32_t* iters, double* gnorm,
+                    int32_t* status, void* stream);
+/* The solver's Hessian as a unit operator: H [Dp][Dp] = I + sum_r w[r] x[idx[r]] x[idx[r]]^T over n rows
+ * (idx null: rows 0..n), both triangles written. */
+int edgedet_svm_hessian(const double* x, int64_t Dp, const int32_t* idx, int64_t n, const double* w, double* H,
+                        void* stream);
+/* out [F][N] = x v[f]: the decision value of every row under every fold's model. */
+int edgedet_svm_decision(const double* x, int64_t N, int64_t Dp, const double* v, int32_t folds, double* out,
+                         void* stream);
+
 /* ------------------------------------------------------------------ image ingest (read_image) */
 /*
  * torchvision.io.read_image(path, ImageReadMode.RGB) of detect.py:55-58 for baseline JPEGs, split
