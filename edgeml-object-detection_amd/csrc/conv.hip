@@ -17,6 +17,7 @@
 // for the b128 lane groups).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.hpp"
 
@@ -1408,6 +1409,27 @@ static bool x6b_presplit(const ConvParams& p) {
 }
 
 
+// The kernel variant of an x6b problem: XF an input transform is fused, UT Cin is a multiple of the
+// 32-deep stage, P1 a dense 1x1 input (conv_x6b_body).
+struct X6bVariant {
+    bool xf, ut, p1;
+    bool operator==(const X6bVariant& o) const { return xf == o.xf && ut == o.ut && p1 == o.p1; }
+};
+static X6bVariant x6b_variant(const ConvParams& p) {
+    return {p.in_scale || p.in_shift || p.in_relu, p.Cin % BK6B == 0,
+            p.lin_x && p.KH == 1 && p.KW == 1 && p.Cin % 4 == 0};
+}
+// kernel(XF, UT, P1) for the variant's flags as compile-time constants (std::bool_constant): all eight
+// kernels are instantiated, the variant's is returned.
+template <typename F>
+static auto x6b_select(X6bVariant v, F kernel) {
+    using T = std::true_type;
+    using N = std::false_type;
+    auto p1 = [&](auto xf, auto ut) { return v.p1 ? kernel(xf, ut, T{}) : kernel(xf, ut, N{}); };
+    auto ut = [&](auto xf) { return v.ut ? p1(xf, T{}) : p1(xf, N{}); };
+    return v.xf ? ut(T{}) : ut(N{});
+}
+
 template <int BM = 256, int PF = 1, int BN = 128>
 static int launch_x6b(const ConvParams& p0, hipStream_t s) {
     ConvParams p = p0;
@@ -1418,21 +1440,19 @@ static int launch_x6b(const ConvParams& p0, hipStream_t s) {
                         "conv split-K: 2 halves, no residual, no activation (y must be zeroed)");
     const int64_t nwg = cdiv(p.M, BM) * cdiv(p.Cout, BN) * (p.ksplit > 1 ? 2 : 1);
     EDGEDET_REQUIRE(nwg < (1ll << 31), "conv grid too large");
-    const bool xf = p.in_scale || p.in_shift || p.in_relu, ut = p.Cin % BK6B == 0;
+    const X6bVariant v = x6b_variant(p);
     if (BM == 256 && BN == 128 && x6b_presplit(p)) {
         const int64_t items = (int64_t)p.B * p.H * p.W * (p.Cin / 8);
         const unsigned g = (unsigned)std::min<int64_t>(cdiv(items, 256), 256 * 64);
-        hipLaunchKernelGGL(xf ? split_act_kernel<true> : split_act_kernel<false>, dim3(g), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(v.xf ? split_act_kernel<true> : split_act_kernel<false>, dim3(g), dim3(256), 0, s, p);
         EDGEDET_LAUNCH_CHECK();
         hipLaunchKernelGGL((conv_x6b_kernel<false, true, true>), dim3((unsigned)nwg), dim3(512), 0, s, p);
         EDGEDET_LAUNCH_CHECK();
         return 0;
     }
-    const bool p1 = p.lin_x && p.KH == 1 && p.KW == 1 && p.Cin % 4 == 0;
-    auto k = p1 ? (xf ? (ut ? conv_x6b_kernel<true, true, false, BM, PF, true, BN> : conv_x6b_kernel<true, false, false, BM, PF, true, BN>)
-                      : (ut ? conv_x6b_kernel<false, true, false, BM, PF, true, BN> : conv_x6b_kernel<false, false, false, BM, PF, true, BN>))
-         : xf ? (ut ? conv_x6b_kernel<true, true, false, BM, PF, false, BN> : conv_x6b_kernel<true, false, false, BM, PF, false, BN>)
-              : (ut ? conv_x6b_kernel<false, true, false, BM, PF, false, BN> : conv_x6b_kernel<false, false, false, BM, PF, false, BN>);
+    auto k = x6b_select(v, [](auto xf, auto ut, auto p1) {
+        return conv_x6b_kernel<decltype(xf)::value, decltype(ut)::value, false, BM, PF, decltype(p1)::value, BN>;
+    });
     hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), 0, s, p);
     EDGEDET_LAUNCH_CHECK();
     return 0;
@@ -1440,26 +1460,21 @@ static int launch_x6b(const ConvParams& p0, hipStream_t s) {
 
 template <int BM, int BN>
 static int launch_x6b_group(ConvGroup& g, hipStream_t s) {
-    const ConvParams& p = g.p[0];
-    const bool xf = p.in_scale || p.in_shift || p.in_relu, ut = p.Cin % BK6B == 0;
-    const bool p1 = p.lin_x && p.KH == 1 && p.KW == 1 && p.Cin % 4 == 0;
+    const X6bVariant v = x6b_variant(g.p[0]);
     int64_t total = 0;
     for (int k = 0; k < g.n; ++k) {
         const ConvParams& q = g.p[k];
         EDGEDET_REQUIRE(q.w3 && ((uintptr_t)q.w3 & 15) == 0 && q.Kpad % BK6B == 0 && q.ksplit <= 1,
                         "conv group: bf16x6 members with 16-byte aligned split planes, Kpad % 32 == 0, no split-K");
-        const bool qxf = q.in_scale || q.in_shift || q.in_relu, qut = q.Cin % BK6B == 0;
-        const bool qp1 = q.lin_x && q.KH == 1 && q.KW == 1 && q.Cin % 4 == 0;
-        EDGEDET_REQUIRE(qxf == xf && qut == ut && qp1 == p1, "conv group: members of one kernel variant");
+        EDGEDET_REQUIRE(x6b_variant(q) == v, "conv group: members of one kernel variant");
         g.start[k] = (int)total;
         total += cdiv(q.M, BM) * cdiv(q.Cout, BN);
         EDGEDET_REQUIRE(total < (1ll << 31), "conv group grid too large");
     }
     g.start[g.n] = (int)total;
-    auto k = p1 ? (xf ? (ut ? conv_x6b_group_kernel<true, true, BM, true, BN> : conv_x6b_group_kernel<true, false, BM, true, BN>)
-                      : (ut ? conv_x6b_group_kernel<false, true, BM, true, BN> : conv_x6b_group_kernel<false, false, BM, true, BN>))
-         : xf ? (ut ? conv_x6b_group_kernel<true, true, BM, false, BN> : conv_x6b_group_kernel<true, false, BM, false, BN>)
-              : (ut ? conv_x6b_group_kernel<false, true, BM, false, BN> : conv_x6b_group_kernel<false, false, BM, false, BN>);
+    auto k = x6b_select(v, [](auto xf, auto ut, auto p1) {
+        return conv_x6b_group_kernel<decltype(xf)::value, decltype(ut)::value, BM, decltype(p1)::value, BN>;
+    });
     hipLaunchKernelGGL(k, dim3((unsigned)total), dim3(512), 0, s, g);
     EDGEDET_LAUNCH_CHECK();
     return 0;
@@ -1556,8 +1571,8 @@ static int launch_pw_stream(const ConvParams& p, int tile, hipStream_t s) {
     EDGEDET_REQUIRE(p.lin_y && (!p.res || p.lin_res), "pw_stream: dense output and residual rows");
     const int kj = (p.Cin + 7) / 8, nb = (p.Cout + 31) / 32;
     EDGEDET_REQUIRE(nb >= 1 && nb <= 3 && kj <= 9, "pw_stream: Cout <= 96, Cin <= 72");
-    if (tile == 34) return launch_pw_stream_n<1, true>(p, kj, s);
-    if (tile == 35) return launch_pw_stream_n<1, false>(p, kj, s);
+    if (tile == TILE_PW_STREAM_WAVE) return launch_pw_stream_n<1, true>(p, kj, s);
+    if (tile == TILE_PW_STREAM_WAVE_NOPF) return launch_pw_stream_n<1, false>(p, kj, s);
     EDGEDET_REQUIRE(nb * kj <= 18, "pw_stream tile 33: NB x KJ <= 18");
     if (nb == 1) return launch_pw_stream_n<1, true>(p, kj, s);
     if (nb == 2) return launch_pw_stream_n<2, true>(p, kj, s);
@@ -1621,12 +1636,12 @@ int conv_prepare(ConvParams& p) {
 // The kernel variant that runs: the requested tile, or the automatic choice (compute-bound LDS
 // tiles switch to their bf16x6 form when the split weight planes are present).
 int conv_resolve_tile(const ConvParams& p, int tile) {
-    if (tile <= 0) {
+    if (tile <= TILE_AUTO) {
         tile = choose_tile(p);
         if (p.w3 && tile >= 2 && tile <= 4) {
             tile += 20;
             // large problems: the 32-deep-stage 256 x 128 tile (>= 2 workgroups per CU)
-            if (tile >= 23 && cdiv(p.M, 256) * cdiv(p.Cout, 128) >= 512) tile = 25;
+            if (tile >= 23 && cdiv(p.M, 256) * cdiv(p.Cout, 128) >= 512) tile = TILE_X6B_256x128;
         }
     }
     return tile;
@@ -1637,64 +1652,52 @@ int conv_launch(ConvParams p, int tile, hipStream_t s) {
     const int rc = conv_prepare(p);
     if (rc) return rc;
     tile = conv_resolve_tile(p, tile);
+    if (tile >= 10 && tile <= 17)  // the direct and split-K pointwise tiles
+        EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
     switch (tile) {
         case 21: return launch_x6<2, 2, 1, 1>(p, s);  // 64 x 64, bf16x6
         case 22: return launch_x6<2, 2, 2, 1>(p, s);  // 128 x 64, bf16x6
         case 23: return launch_x6<2, 2, 2, 2>(p, s);  // 128 x 128, bf16x6
         case 24: return launch_x6<4, 2, 2, 2>(p, s);  // 256 x 128, bf16x6
-        case 25: return launch_x6b(p, s);             // 256 x 128, bf16x6, 32-deep swizzled stages
         case 27: return launch_x6<4, 2, 1, 1>(p, s);  // 128 x 64, bf16x6, 8 waves (32 x 32 each)
         case 28: return launch_x6<4, 2, 1, 2>(p, s);  // 128 x 128, bf16x6, 8 waves (32 x 64 each)
-        case 29: return launch_x6b<128, 1>(p, s);     // 128 x 128, bf16x6, 32-deep swizzled stages, skewed pipeline
-        case 30: return launch_x6b<128, 2>(p, s);     // the same, two register stages
-        case 31: return launch_x6b<64, 1>(p, s);      // 64 x 128, bf16x6, two workgroups per CU
-        case 32: return launch_x6b<64, 2>(p, s);      // the same, two register stages
-        case 38: return launch_x6b<128, 1, 64>(p, s); // 128 x 64, bf16x6, 32-deep swizzled stages (Cout <= 64 layers)
-        case 39: return launch_x6b<128, 1, 256>(p, s); // 128 x 256: the A panel read once per Cout = 256 layer
-        case 26: {                                    // the same, K split in two halves (atomics into zeroed y)
+        // bf16x6 with 32-deep swizzled stages (the named ids: ConvTile, kernels.hpp)
+        case TILE_X6B_256x128: return launch_x6b(p, s);  // 25: 256 x 128
+        case TILE_X6B_256x128_SPLITK: {                  // 26: the same, K split in two halves (atomics into zeroed y)
             ConvParams q = p;
             q.ksplit = 2;
             return launch_x6b(q, s);
         }
-        case 33:                                      // streaming 1x1, fp32 MFMA, weights in registers
-        case 34:
-        case 35: return launch_pw_stream(p, tile, s);
+        case TILE_X6B_128x128: return launch_x6b<128, 1>(p, s);       // 29: 128 x 128, skewed pipeline
+        case 30: return launch_x6b<128, 2>(p, s);                     // the same, two register stages
+        case TILE_X6B_64x128: return launch_x6b<64, 1>(p, s);         // 31: 64 x 128, two workgroups per CU
+        case 32: return launch_x6b<64, 2>(p, s);                      // the same, two register stages
+        case TILE_X6B_128x64: return launch_x6b<128, 1, 64>(p, s);    // 38: 128 x 64 (Cout <= 64 layers)
+        case TILE_X6B_128x256: return launch_x6b<128, 1, 256>(p, s);  // 39: 128 x 256, the A panel read once per Cout = 256 layer
+        case 33:  // streaming 1x1, fp32 MFMA, weights in registers
+        case TILE_PW_STREAM_WAVE:       // 34
+        case TILE_PW_STREAM_WAVE_NOPF:  // 35
+            return launch_pw_stream(p, tile, s);
         case 1: return launch_cfg<4, 1, 1, 1>(p, s);  // 128 x 32
         case 2: return launch_cfg<2, 2, 2, 1>(p, s);  // 128 x 64
         case 3: return launch_cfg<2, 2, 2, 2>(p, s);  // 128 x 128
         case 4: return launch_cfg<4, 2, 2, 2>(p, s);  // 256 x 128
         case 5: return launch_cfg<2, 2, 1, 1>(p, s);  // 64 x 64
         case 6: return launch_cfg<1, 1, 1, 1>(p, s);  // 32 x 32 (one wave)
-        case 10:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw<2, 2>(p, s);               // direct, 64 x 64 per wave
-        case 11:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw<4, 1>(p, s);               // direct, 128 x 32 per wave
-        case 12:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw<1, 2>(p, s);               // direct, 32 x 64 per wave
-        case 15:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw<2, 1>(p, s);               // direct, 64 x 32 per wave
-        case 13:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw_splitk<1>(p, s);           // split-K over 4 waves, 32 x 32
-        case 16:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw_splitk<1, 8>(p, s);        // split-K over 8 waves, 32 x 32
-        case 17:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw_splitk<2, 8>(p, s);        // split-K over 8 waves, 32 x 64
-        case 14:
-            EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-            return launch_pw_splitk<2>(p, s);           // split-K over 4 waves, 32 x 64
+        case 10: return launch_pw<2, 2>(p, s);         // direct, 64 x 64 per wave
+        case 11: return launch_pw<4, 1>(p, s);         // direct, 128 x 32 per wave
+        case 12: return launch_pw<1, 2>(p, s);         // direct, 32 x 64 per wave
+        case 15: return launch_pw<2, 1>(p, s);         // direct, 64 x 32 per wave
+        case 13: return launch_pw_splitk<1>(p, s);     // split-K over 4 waves, 32 x 32
+        case 16: return launch_pw_splitk<1, 8>(p, s);  // split-K over 8 waves, 32 x 32
+        case 17: return launch_pw_splitk<2, 8>(p, s);  // split-K over 8 waves, 32 x 64
+        case 14: return launch_pw_splitk<2>(p, s);     // split-K over 4 waves, 32 x 64
         default: EDGEDET_REQUIRE(false, "conv: unknown tile config");
     }
 }
 
 // Grouped launch of up to EDGEDET_MAX_GROUP conv problems (exec.hip EDGEDET_OP_GROUP).  Every member
-// must resolve to the same x6b tile (29 / 31 / 38 / 25, no pre-split input) and kernel variant; returns
+// must resolve to the same x6b tile (one of the switch below, no pre-split input) and kernel variant; returns
 // 1 without launching when they do not, and the caller then issues them one by one.
 int conv_group_launch(const ConvParams* ps, int n, int tile, hipStream_t s) {
     EDGEDET_REQUIRE(n >= 1 && n <= EDGEDET_MAX_GROUP, "conv group: 1..EDGEDET_MAX_GROUP members");
@@ -1710,11 +1713,11 @@ int conv_group_launch(const ConvParams* ps, int n, int tile, hipStream_t s) {
         if (t != t0 || gl.p[k].x3) return 1;
     }
     switch (t0) {
-        case 25: return launch_x6b_group<256, 128>(gl, s);
-        case 29: return launch_x6b_group<128, 128>(gl, s);
-        case 31: return launch_x6b_group<64, 128>(gl, s);
-        case 38: return launch_x6b_group<128, 64>(gl, s);
-        case 39: return launch_x6b_group<128, 256>(gl, s);
+        case TILE_X6B_256x128: return launch_x6b_group<256, 128>(gl, s);
+        case TILE_X6B_128x128: return launch_x6b_group<128, 128>(gl, s);
+        case TILE_X6B_64x128: return launch_x6b_group<64, 128>(gl, s);
+        case TILE_X6B_128x64: return launch_x6b_group<128, 64>(gl, s);
+        case TILE_X6B_128x256: return launch_x6b_group<128, 256>(gl, s);
         default: return 1;
     }
 }

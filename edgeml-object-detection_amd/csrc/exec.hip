@@ -5,57 +5,7 @@
 // it on the caller's stream, or captures the whole sequence once into a hipGraph that is replayed
 // per batch (one host call per forward; no allocation, no sync, no host round trip inside).
 //
-// Record layouts (i = int64 fields, p = device pointers, d = doubles, f = floats):
-//   MEMSET         p0 ptr; i0 bytes
-//   PREPROCESS     p0 x[B,3,H,W] f32 | 0; p2 x[B,3,H,W] u8 | 0 (exactly one); p1 y[B,Hp,Wp,4]; i0..6 B,H,W,Ho,Wo,Hp,Wp; f0..2 mean; f3..5 std
-//   CONV           p0 x; p1 w[Cout][Kpad]; p2 bias; p3 y; p4 res|0; p5 in_scale|0; p6 w3 bf16 planes|0;
-//                  p7 in_shift|0; i24 in_relu; p8 x3 scratch [3][B*H*W*Cin] bf16 | 0 (pre-split input
-//                  planes for the 256 x 128 bf16x6 tile: the split and the input transform run once
-//                  per input element instead of once per N tile)
-//                  i0..11 B,H,W,Cin,Ho,Wo,Cout,KH,KW,stride,pad,act; i12 K; i13 Kpad;
-//                  i14..16 x/y/res pixel strides; i17..19 x/y/res batch strides; i20 y offset;
-//                  i21..22 res_H,res_W (nearest upsample source, 0 = same); i23 tile (0 = auto);
-//                  p9 timing probe slot (2 x u64; bf16x6 tiles only; 0 in product plans)
-//   SSD_STEM       p0 x NHWC4; p1 w0 [16][i5]; p2 b0; p3 wd [9][16]; p4 bd; p5 w1 [16][i6]; p6 b1; p7 y;
-//                  i0..4 B,H,W,Ho,Wo (SSDLite features.0.0 + features.0.1 fused)
-//   DWCONV         p0 x; p1 w[K*K][C]; p2 bias; p3 y; p4 SE partial sums [B,16,C] | 0;
-//                  i0..9 B,H,W,C,Ho,Wo,K,stride,pad,act; i10 SE partial-sum splits (0 = 16)
-//   MBCONV         InvertedResidual without SE in one kernel: p0 x; p1 expand w [Cexp][i12]; p2 b1;
-//                  p3 dw w [K*K][Cexp]; p4 bd; p5 project w [Cout][i13]; p6 b2; p7 y;
-//                  i0..11 B,H,W,Cin,Cexp,Cout,Ho,Wo,K,stride,pad,act; i14 residual
-//   CHANNEL_MEAN   p0 x[B,HW,C]; p1 mean[B,C]; i0..2 B,HW,C
-//   SE_FC          p0 part[B,16,C]; p1 w1[S][C]; p2 b1; p3 w2t[S][C]; p4 b2; p5 scale[B,C]; p6 hidden[B,S];
-//                  i0..4 B,C,S,HW,splits (0 = 16)
-//   MAXPOOL        p0 x; p1 y; i0..8 B,H,W,C,Ho,Wo,K,stride,pad
-//   SSD_SCORES     p0 logits[B,A,NC]; p1 reg[B,A,4]; p2 anchors[A,4]; p3 scores_t[B,NC,A];
-//                  p4 boxes[B,A,4]; i0..2 B,A,NC; f0,f1 img_h,img_w
-//   SSD_CLASS_NMS  p0 scores_t; p1 boxes; p2..6 records (box,score,tb,label,count);
-//                  i0..4 B,A,NC,topk,kmax; f0 score_thresh; d0 iou
-//   MERGE_TOPK     p0..4 records; p5 ratio[B,2]|0; p6 out_box; p7 out_score; p8 out_label|0;
-//                  p9 out_count; i0..3 B,S,kmax,N
-//   RPN_LEVEL_NMS  p0..4 objectness [B][n] per level; p5..9 anchors per level; p10..14 records;
-//                  p15..19 deltas [B][n][4] per level; i0..5 B,nlevels,(unused),A,topk,kmax; i6..10 n per level;
-//                  f0..3 img_h,img_w,min_size,score_thresh; d0 iou; chunked top-k (optional): p20 ckey,
-//                  p21 cidx [B,levels,nchunk,1024], p22 ccount [B,levels,nchunk]; i16 chunk; i17 nchunk;
-//                  split NMS scratch (optional) p23 [rpn_split_bytes(B * levels)]
-//   ROI_ALIGN      p0..3 feats; p4 rois; p5 counts; p6 out; i0..10 mode,R,RMAX,B,C,PH,PW,sr,nlevels,
-//                  k_min,k_max; i11..14 H; i15..18 W; f0..3 scales
-//   BOX_SCORES     p0 pred; p1 props; p2 counts; p3 scores; p4 boxes; i0..5 ld,B,R,NC,cls_off,delta_off;
-//                  f0,f1 img_h,img_w
-//   BOX_CLASS_NMS  p0 scores; p1 boxes; p2 counts; p3..7 records; i0..3 B,R,NC,kmax;
-//                  f0 score_thresh; f1 min_size; d0 iou
-//   SSD_POSTPROCESS p0 scores_t; p1 boxes; p2 pool_key; p3 pool_ref; p4 ratio|0; p5 out_box; p6 out_score;
-//                  p7 out_label|0; p8 out_count; i0..4 B,A,NC,topk,N; i5 1 = one-wave class select;
-//                  f0 score_thresh; d0 iou
-//   GN_STATS       p0 x[B,HW,C]; p1 gamma; p2 beta; p3 scale[B,C]; p4 shift[B,C]; i0..3 B,HW,C,G; f0 eps
-//   RETINA_SELECT  p0 logits[B,Atot,K]; p1 deltas[B,Atot,4]; p2 anchors[Atot,4]; p3..7 records
-//                  (box,score,tb,label,count) [B,L,kmax]; i0..4 B,L,Atot,K,topk; i5 kmax; i6..10 a0 per level;
-//                  i11..15 anchors per level; f0,f1 img_h,img_w; f2 score_thresh; p8..10 chunk scratch
-//                  (keys, flat indices [B,L,nchunk,1024], counts [B,L,nchunk]); i16 chunk; i17 nchunk
-//   RETINA_CLASS_NMS p0..4 level records (box,score,tb,label,count); p5..9 class records [B,K,kmax];
-//                  i0..4 B,L,kin,K,kmax; d0 iou
-//   FORK / JOIN    i0 number of side lanes; i47 of every other record = its lane (0 = caller's stream)
-//   WAIT           lane i0 waits for everything issued so far on lane i1 (both forked, or 0)
+// Record layouts (which slot of i / p / f / d holds what, per kind): csrc/records.hpp.
 #include <cstdlib>
 #include <memory>
 #include <mutex>
@@ -67,6 +17,7 @@
 #include <utility>
 
 #include "kernels.hpp"
+#include "records.hpp"
 
 namespace edgedet {
 
@@ -79,79 +30,82 @@ static T* P(const edgedet_op& o, int k) {
     return reinterpret_cast<T*>(static_cast<uintptr_t>(o.p[k]));
 }
 
+// The record list whose five pointers start at slot k0 (a kind's records0, rec::seg order).
 static SegOut seg_out(const edgedet_op& o, int k0, int kmax) {
     SegOut s;
-    s.box = P<f32x4>(o, k0);
-    s.score = P<float>(o, k0 + 1);
-    s.tb = P<uint32_t>(o, k0 + 2);
-    s.label = P<int>(o, k0 + 3);
-    s.count = P<int>(o, k0 + 4);
+    s.box = P<f32x4>(o, k0 + rec::seg::box);
+    s.score = P<float>(o, k0 + rec::seg::score);
+    s.tb = P<uint32_t>(o, k0 + rec::seg::tb);
+    s.label = P<int>(o, k0 + rec::seg::label);
+    s.count = P<int>(o, k0 + rec::seg::count);
     s.kmax = kmax;
     return s;
 }
 
-// CONV record -> ConvParams (layout in the header comment above).
+// CONV record -> ConvParams.
 static ConvParams conv_params(const edgedet_op& o) {
+    namespace r = rec::conv;
     const int64_t* I = o.i;
     ConvParams p{};
-    p.x = P<const float>(o, 0);
-    p.w = P<const float>(o, 1);
-    p.bias = P<const float>(o, 2);
-    p.y = P<float>(o, 3);
-    p.res = P<const float>(o, 4);
-    p.in_scale = P<const float>(o, 5);
-    p.w3 = P<const void>(o, 6);
-    p.in_shift = P<const float>(o, 7);
-    p.in_relu = (int)I[24];
-    p.x3 = P<void>(o, 8);
-    p.stamp = P<unsigned long long>(o, 9);
-    p.B = (int)I[0];
-    p.H = (int)I[1];
-    p.W = (int)I[2];
-    p.Cin = (int)I[3];
-    p.Ho = (int)I[4];
-    p.Wo = (int)I[5];
-    p.Cout = (int)I[6];
-    p.KH = (int)I[7];
-    p.KW = (int)I[8];
-    p.stride = (int)I[9];
-    p.pad = (int)I[10];
-    p.act = (int)I[11];
-    p.K = (int)I[12];
-    p.Kpad = (int)I[13];
-    p.x_pstride = (int)I[14];
-    p.y_pstride = (int)I[15];
-    p.res_pstride = (int)I[16];
-    p.x_bstride = I[17];
-    p.y_bstride = I[18];
-    p.res_bstride = I[19];
-    p.y_off = I[20];
-    p.res_H = (int)I[21];
-    p.res_W = (int)I[22];
+    p.x = P<const float>(o, r::x);
+    p.w = P<const float>(o, r::w);
+    p.bias = P<const float>(o, r::bias);
+    p.y = P<float>(o, r::y);
+    p.res = P<const float>(o, r::res);
+    p.in_scale = P<const float>(o, r::in_scale);
+    p.w3 = P<const void>(o, r::w3);
+    p.in_shift = P<const float>(o, r::in_shift);
+    p.in_relu = (int)I[r::in_relu];
+    p.x3 = P<void>(o, r::x3);
+    p.stamp = P<unsigned long long>(o, r::stamp);
+    p.B = (int)I[r::B];
+    p.H = (int)I[r::H];
+    p.W = (int)I[r::W];
+    p.Cin = (int)I[r::Cin];
+    p.Ho = (int)I[r::Ho];
+    p.Wo = (int)I[r::Wo];
+    p.Cout = (int)I[r::Cout];
+    p.KH = (int)I[r::KH];
+    p.KW = (int)I[r::KW];
+    p.stride = (int)I[r::stride];
+    p.pad = (int)I[r::pad];
+    p.act = (int)I[r::act];
+    p.K = (int)I[r::K];
+    p.Kpad = (int)I[r::Kpad];
+    p.x_pstride = (int)I[r::x_pstride];
+    p.y_pstride = (int)I[r::y_pstride];
+    p.res_pstride = (int)I[r::res_pstride];
+    p.x_bstride = I[r::x_bstride];
+    p.y_bstride = I[r::y_bstride];
+    p.res_bstride = I[r::res_bstride];
+    p.y_off = I[r::y_off];
+    p.res_H = (int)I[r::res_H];
+    p.res_W = (int)I[r::res_W];
     p.M = p.B * p.Ho * p.Wo;
     return p;
 }
 
 // DWCONV record -> DwParams.
 static DwParams dw_params(const edgedet_op& o) {
+    namespace r = rec::dwconv;
     const int64_t* I = o.i;
     DwParams p{};
-    p.x = P<const float>(o, 0);
-    p.w = P<const float>(o, 1);
-    p.bias = P<const float>(o, 2);
-    p.y = P<float>(o, 3);
-    p.part = P<float>(o, 4);
-    p.B = (int)I[0];
-    p.H = (int)I[1];
-    p.W = (int)I[2];
-    p.C = (int)I[3];
-    p.Ho = (int)I[4];
-    p.Wo = (int)I[5];
-    p.K = (int)I[6];
-    p.stride = (int)I[7];
-    p.pad = (int)I[8];
-    p.act = (int)I[9];
-    p.parts = I[10] > 0 ? (int)I[10] : SE_PARTS;
+    p.x = P<const float>(o, r::x);
+    p.w = P<const float>(o, r::w);
+    p.bias = P<const float>(o, r::bias);
+    p.y = P<float>(o, r::y);
+    p.part = P<float>(o, r::part);
+    p.B = (int)I[r::B];
+    p.H = (int)I[r::H];
+    p.W = (int)I[r::W];
+    p.C = (int)I[r::C];
+    p.Ho = (int)I[r::Ho];
+    p.Wo = (int)I[r::Wo];
+    p.K = (int)I[r::K];
+    p.stride = (int)I[r::stride];
+    p.pad = (int)I[r::pad];
+    p.act = (int)I[r::act];
+    p.parts = I[r::parts] > 0 ? (int)I[r::parts] : SE_PARTS;
     return p;
 }
 
@@ -191,261 +145,294 @@ static int run_op(const edgedet_op& o, hipStream_t s) {
     const int64_t* I = o.i;
     if ((diag_skip_mask() >> (o.kind & 63)) & 1 && o.kind != EDGEDET_OP_FORK && o.kind != EDGEDET_OP_JOIN) return 0;
     switch (o.kind) {
-        case EDGEDET_OP_MEMSET:
-            EDGEDET_CHECK_HIP(hipMemsetAsync(P<void>(o, 0), 0, (size_t)I[0], s));
+        case EDGEDET_OP_MEMSET: {
+            namespace r = rec::mem_set;
+            EDGEDET_CHECK_HIP(hipMemsetAsync(P<void>(o, r::ptr), 0, (size_t)I[r::bytes], s));
             return 0;
+        }
         case EDGEDET_OP_PREPROCESS: {
+            namespace r = rec::preprocess;
             PreParams p{};
-            p.x = P<const float>(o, 0);
-            p.y = P<float>(o, 1);
-            p.xu8 = P<const uint8_t>(o, 2);
-            p.B = (int)I[0];
-            p.H = (int)I[1];
-            p.W = (int)I[2];
-            p.Ho = (int)I[3];
-            p.Wo = (int)I[4];
-            p.Hp = (int)I[5];
-            p.Wp = (int)I[6];
+            p.x = P<const float>(o, r::x);
+            p.y = P<float>(o, r::y);
+            p.xu8 = P<const uint8_t>(o, r::xu8);
+            p.B = (int)I[r::B];
+            p.H = (int)I[r::H];
+            p.W = (int)I[r::W];
+            p.Ho = (int)I[r::Ho];
+            p.Wo = (int)I[r::Wo];
+            p.Hp = (int)I[r::Hp];
+            p.Wp = (int)I[r::Wp];
             for (int c = 0; c < 3; ++c) {
-                p.mean[c] = o.f[c];
-                p.stdv[c] = o.f[3 + c];
+                p.mean[c] = o.f[r::mean0 + c];
+                p.stdv[c] = o.f[r::std0 + c];
             }
             return preprocess_launch(p, s);
         }
         case EDGEDET_OP_MBCONV: {
+            namespace r = rec::mbconv;
             MbParams p{};
-            p.x = P<const float>(o, 0);
-            p.w1 = P<const float>(o, 1);
-            p.b1 = P<const float>(o, 2);
-            p.wd = P<const float>(o, 3);
-            p.bd = P<const float>(o, 4);
-            p.w2 = P<const float>(o, 5);
-            p.b2 = P<const float>(o, 6);
-            p.y = P<float>(o, 7);
-            p.B = (int)I[0];
-            p.H = (int)I[1];
-            p.W = (int)I[2];
-            p.Cin = (int)I[3];
-            p.Cexp = (int)I[4];
-            p.Cout = (int)I[5];
-            p.Ho = (int)I[6];
-            p.Wo = (int)I[7];
-            p.K = (int)I[8];
-            p.stride = (int)I[9];
-            p.pad = (int)I[10];
-            p.act = (int)I[11];
-            p.ld1 = (int)I[12];
-            p.ld2 = (int)I[13];
-            p.residual = (int)I[14];
+            p.x = P<const float>(o, r::x);
+            p.w1 = P<const float>(o, r::w1);
+            p.b1 = P<const float>(o, r::b1);
+            p.wd = P<const float>(o, r::wd);
+            p.bd = P<const float>(o, r::bd);
+            p.w2 = P<const float>(o, r::w2);
+            p.b2 = P<const float>(o, r::b2);
+            p.y = P<float>(o, r::y);
+            p.B = (int)I[r::B];
+            p.H = (int)I[r::H];
+            p.W = (int)I[r::W];
+            p.Cin = (int)I[r::Cin];
+            p.Cexp = (int)I[r::Cexp];
+            p.Cout = (int)I[r::Cout];
+            p.Ho = (int)I[r::Ho];
+            p.Wo = (int)I[r::Wo];
+            p.K = (int)I[r::K];
+            p.stride = (int)I[r::stride];
+            p.pad = (int)I[r::pad];
+            p.act = (int)I[r::act];
+            p.ld1 = (int)I[r::ld1];
+            p.ld2 = (int)I[r::ld2];
+            p.residual = (int)I[r::residual];
             return mbconv_launch(p, s);
         }
         case EDGEDET_OP_CONV: {
-            if ((diag_skip_masks()[1] >> (I[23] & 63)) & 1) return 0;
+            const int tile = (int)I[rec::conv::tile];
+            if ((diag_skip_masks()[1] >> (tile & 63)) & 1) return 0;
             const ConvParams p = conv_params(o);
             EDGEDET_REQUIRE(p.K == p.KH * p.KW * p.Cin, "conv: K != KH*KW*Cin");
-            return conv_launch(p, (int)I[23], s);
+            return conv_launch(p, tile, s);
         }
         case EDGEDET_OP_DWCONV:
             return dwconv_launch(dw_params(o), s);
-        case EDGEDET_OP_CHANNEL_MEAN:
-            return channel_mean_launch(P<const float>(o, 0), P<float>(o, 1), (int)I[0], (int)I[1], (int)I[2], s);
-        case EDGEDET_OP_SE_FC:
-            return se_fc_launch(P<const float>(o, 0), P<const float>(o, 1), P<const float>(o, 2), P<const float>(o, 3),
-                                P<const float>(o, 4), P<float>(o, 6), P<float>(o, 5), (int)I[0], (int)I[1], (int)I[2],
-                                (int)I[3], I[4] > 0 ? (int)I[4] : SE_PARTS, s);
+        case EDGEDET_OP_CHANNEL_MEAN: {
+            namespace r = rec::channel_mean;
+            return channel_mean_launch(P<const float>(o, r::x), P<float>(o, r::mean), (int)I[r::B], (int)I[r::HW],
+                                       (int)I[r::C], s);
+        }
+        case EDGEDET_OP_SE_FC: {
+            namespace r = rec::se_fc;
+            return se_fc_launch(P<const float>(o, r::part), P<const float>(o, r::w1), P<const float>(o, r::b1),
+                                P<const float>(o, r::w2t), P<const float>(o, r::b2), P<float>(o, r::hidden),
+                                P<float>(o, r::scale), (int)I[r::B], (int)I[r::C], (int)I[r::S], (int)I[r::HW],
+                                I[r::parts] > 0 ? (int)I[r::parts] : SE_PARTS, s);
+        }
         case EDGEDET_OP_MAXPOOL: {
+            namespace r = rec::maxpool;
             PoolParams p{};
-            p.x = P<const float>(o, 0);
-            p.y = P<float>(o, 1);
-            p.B = (int)I[0];
-            p.H = (int)I[1];
-            p.W = (int)I[2];
-            p.C = (int)I[3];
-            p.Ho = (int)I[4];
-            p.Wo = (int)I[5];
-            p.K = (int)I[6];
-            p.stride = (int)I[7];
-            p.pad = (int)I[8];
+            p.x = P<const float>(o, r::x);
+            p.y = P<float>(o, r::y);
+            p.B = (int)I[r::B];
+            p.H = (int)I[r::H];
+            p.W = (int)I[r::W];
+            p.C = (int)I[r::C];
+            p.Ho = (int)I[r::Ho];
+            p.Wo = (int)I[r::Wo];
+            p.K = (int)I[r::K];
+            p.stride = (int)I[r::stride];
+            p.pad = (int)I[r::pad];
             return maxpool_launch(p, s);
         }
-        case EDGEDET_OP_SSD_SCORES:
-            return ssd_scores_launch(P<const float>(o, 0), P<const float>(o, 1), P<const float>(o, 2), P<float>(o, 3),
-                                     P<float>(o, 4), (int)I[0], (int)I[1], (int)I[2], o.f[0], o.f[1], s);
-        case EDGEDET_OP_SSD_CLASS_NMS:
-            return ssd_class_nms_launch(P<const float>(o, 0), P<const float>(o, 1), (int)I[0], (int)I[1], (int)I[2],
-                                        o.f[0], (int)I[3], o.d[0], seg_out(o, 2, (int)I[4]), s);
+        case EDGEDET_OP_SSD_SCORES: {
+            namespace r = rec::ssd_scores;
+            return ssd_scores_launch(P<const float>(o, r::logits), P<const float>(o, r::reg),
+                                     P<const float>(o, r::anchors), P<float>(o, r::scores_t), P<float>(o, r::boxes),
+                                     (int)I[r::B], (int)I[r::A], (int)I[r::NC], o.f[r::img_h], o.f[r::img_w], s);
+        }
+        case EDGEDET_OP_SSD_CLASS_NMS: {
+            namespace r = rec::ssd_class_nms;
+            return ssd_class_nms_launch(P<const float>(o, r::scores_t), P<const float>(o, r::boxes), (int)I[r::B],
+                                        (int)I[r::A], (int)I[r::NC], o.f[r::score_thresh], (int)I[r::topk],
+                                        o.d[r::iou], seg_out(o, r::records0, (int)I[r::kmax]), s);
+        }
         case EDGEDET_OP_MERGE_TOPK: {
+            namespace r = rec::merge_topk;
             MergeParams p{};
-            p.box = P<const f32x4>(o, 0);
-            p.score = P<const float>(o, 1);
-            p.tb = P<const uint32_t>(o, 2);
-            p.label = P<const int>(o, 3);
-            p.count = P<const int>(o, 4);
-            p.ratio = P<const float>(o, 5);
-            p.out_box = P<float>(o, 6);
-            p.out_score = P<float>(o, 7);
-            p.out_label = P<int64_t>(o, 8);
-            p.out_count = P<int>(o, 9);
-            p.S = (int)I[1];
-            p.kmax = (int)I[2];
-            p.N = (int)I[3];
-            return merge_topk_launch(p, (int)I[0], s);
+            p.box = P<const f32x4>(o, r::records0 + rec::seg::box);
+            p.score = P<const float>(o, r::records0 + rec::seg::score);
+            p.tb = P<const uint32_t>(o, r::records0 + rec::seg::tb);
+            p.label = P<const int>(o, r::records0 + rec::seg::label);
+            p.count = P<const int>(o, r::records0 + rec::seg::count);
+            p.ratio = P<const float>(o, r::ratio);
+            p.out_box = P<float>(o, r::out_box);
+            p.out_score = P<float>(o, r::out_score);
+            p.out_label = P<int64_t>(o, r::out_label);
+            p.out_count = P<int>(o, r::out_count);
+            p.S = (int)I[r::S];
+            p.kmax = (int)I[r::kmax];
+            p.N = (int)I[r::N];
+            return merge_topk_launch(p, (int)I[r::B], s);
         }
         case EDGEDET_OP_RPN_LEVEL_NMS: {
+            namespace r = rec::rpn_level_nms;
             RpnParams p{};
-            p.B = (int)I[0];
-            p.nlevels = (int)I[1];
-            p.ld = (int)I[2];
-            p.A = (int)I[3];
-            p.topk = (int)I[4];
+            p.B = (int)I[r::B];
+            p.nlevels = (int)I[r::nlevels];
+            p.ld = (int)I[r::ld];
+            p.A = (int)I[r::A];
+            p.topk = (int)I[r::topk];
             EDGEDET_REQUIRE(p.nlevels >= 1 && p.nlevels <= 5, "rpn: 1..5 levels");
             for (int l = 0; l < p.nlevels; ++l) {
-                p.lv[l].obj = P<const float>(o, l);
-                p.lv[l].deltas = P<const float>(o, 15 + l);
-                p.lv[l].anchors = P<const float>(o, 5 + l);
-                p.lv[l].n = (int)I[6 + l];
+                p.lv[l].obj = P<const float>(o, r::obj0 + l);
+                p.lv[l].deltas = P<const float>(o, r::deltas0 + l);
+                p.lv[l].anchors = P<const float>(o, r::anchors0 + l);
+                p.lv[l].n = (int)I[r::n0 + l];
             }
-            p.img_h = o.f[0];
-            p.img_w = o.f[1];
-            p.min_size = o.f[2];
-            p.score_thresh = o.f[3];
-            p.iou = make_iou_thr(o.d[0]);
-            p.ckey = P<uint32_t>(o, 20);  // chunked top-k scratch (or null)
-            p.cidx = P<int>(o, 21);
-            p.ccount = P<int>(o, 22);
-            p.chunk = (int)I[16];
-            p.nchunk = (int)I[17];
-            p.split = P<void>(o, 23);
-            return rpn_level_nms_launch(p, seg_out(o, 10, (int)I[5]), s);
+            p.img_h = o.f[r::img_h];
+            p.img_w = o.f[r::img_w];
+            p.min_size = o.f[r::min_size];
+            p.score_thresh = o.f[r::score_thresh];
+            p.iou = make_iou_thr(o.d[r::iou]);
+            p.ckey = P<uint32_t>(o, r::ckey);  // chunked top-k scratch (or null)
+            p.cidx = P<int>(o, r::cidx);
+            p.ccount = P<int>(o, r::ccount);
+            p.chunk = (int)I[r::chunk];
+            p.nchunk = (int)I[r::nchunk];
+            p.split = P<void>(o, r::split);
+            return rpn_level_nms_launch(p, seg_out(o, r::records0, (int)I[r::kmax]), s);
         }
         case EDGEDET_OP_ROI_ALIGN: {
+            namespace r = rec::roi_align;
             RoiParams p{};
             for (int l = 0; l < 4; ++l) {
-                p.feat[l] = P<const float>(o, l);
-                p.H[l] = (int)I[11 + l];
-                p.W[l] = (int)I[15 + l];
-                p.scale[l] = o.f[l];
+                p.feat[l] = P<const float>(o, r::feat0 + l);
+                p.H[l] = (int)I[r::H0 + l];
+                p.W[l] = (int)I[r::W0 + l];
+                p.scale[l] = o.f[r::scale0 + l];
             }
-            p.rois = P<const float>(o, 4);
-            p.counts = P<const int>(o, 5);
-            p.out = P<float>(o, 6);
-            p.mode = (int)I[0];
-            p.R = (int)I[1];
-            p.RMAX = (int)I[2];
-            p.B = (int)I[3];
-            p.C = (int)I[4];
-            p.PH = (int)I[5];
-            p.PW = (int)I[6];
-            p.sr = (int)I[7];
-            p.nlevels = (int)I[8];
-            p.k_min = (int)I[9];
-            p.k_max = (int)I[10];
+            p.rois = P<const float>(o, r::rois);
+            p.counts = P<const int>(o, r::counts);
+            p.out = P<float>(o, r::out);
+            p.mode = (int)I[r::mode];
+            p.R = (int)I[r::R];
+            p.RMAX = (int)I[r::RMAX];
+            p.B = (int)I[r::B];
+            p.C = (int)I[r::C];
+            p.PH = (int)I[r::PH];
+            p.PW = (int)I[r::PW];
+            p.sr = (int)I[r::sr];
+            p.nlevels = (int)I[r::nlevels];
+            p.k_min = (int)I[r::k_min];
+            p.k_max = (int)I[r::k_max];
             return roi_align_launch(p, s);
         }
-        case EDGEDET_OP_BOX_SCORES:
-            return box_scores_launch(P<const float>(o, 0), (int)I[0], (int)I[4], (int)I[5], P<const float>(o, 1),
-                                     P<const int>(o, 2), P<float>(o, 3), P<float>(o, 4), (int)I[1], (int)I[2],
-                                     (int)I[3], o.f[0], o.f[1], s);
-        case EDGEDET_OP_BOX_CLASS_NMS:
-            return box_class_nms_launch(P<const float>(o, 0), P<const float>(o, 1), P<const int>(o, 2), (int)I[0],
-                                        (int)I[1], (int)I[2], o.f[0], o.f[1], o.d[0], seg_out(o, 3, (int)I[3]), s);
+        case EDGEDET_OP_BOX_SCORES: {
+            namespace r = rec::box_scores;
+            return box_scores_launch(P<const float>(o, r::pred), (int)I[r::ld], (int)I[r::cls_off],
+                                     (int)I[r::delta_off], P<const float>(o, r::props), P<const int>(o, r::counts),
+                                     P<float>(o, r::scores), P<float>(o, r::boxes), (int)I[r::B], (int)I[r::R],
+                                     (int)I[r::NC], o.f[r::img_h], o.f[r::img_w], s);
+        }
+        case EDGEDET_OP_BOX_CLASS_NMS: {
+            namespace r = rec::box_class_nms;
+            return box_class_nms_launch(P<const float>(o, r::scores), P<const float>(o, r::boxes),
+                                        P<const int>(o, r::counts), (int)I[r::B], (int)I[r::R], (int)I[r::NC],
+                                        o.f[r::score_thresh], o.f[r::min_size], o.d[r::iou],
+                                        seg_out(o, r::records0, (int)I[r::kmax]), s);
+        }
         case EDGEDET_OP_GN_STATS: {
+            namespace r = rec::gn_stats;
             GnParams p{};
-            p.x = P<const float>(o, 0);
-            p.gamma = P<const float>(o, 1);
-            p.beta = P<const float>(o, 2);
-            p.scale = P<float>(o, 3);
-            p.shift = P<float>(o, 4);
-            p.B = (int)I[0];
-            p.HW = (int)I[1];
-            p.C = (int)I[2];
-            p.G = (int)I[3];
-            p.eps = o.f[0];
+            p.x = P<const float>(o, r::x);
+            p.gamma = P<const float>(o, r::gamma);
+            p.beta = P<const float>(o, r::beta);
+            p.scale = P<float>(o, r::scale);
+            p.shift = P<float>(o, r::shift);
+            p.B = (int)I[r::B];
+            p.HW = (int)I[r::HW];
+            p.C = (int)I[r::C];
+            p.G = (int)I[r::G];
+            p.eps = o.f[r::eps];
             return gn_stats_launch(p, s);
         }
         case EDGEDET_OP_RETINA_SELECT: {
+            namespace r = rec::retina_select;
             RetinaSelParams p{};
-            p.logits = P<const float>(o, 0);
-            p.deltas = P<const float>(o, 1);
-            p.anchors = P<const float>(o, 2);
-            p.B = (int)I[0];
-            p.L = (int)I[1];
-            p.Atot = (int)I[2];
-            p.K = (int)I[3];
-            p.topk = (int)I[4];
+            p.logits = P<const float>(o, r::logits);
+            p.deltas = P<const float>(o, r::deltas);
+            p.anchors = P<const float>(o, r::anchors);
+            p.B = (int)I[r::B];
+            p.L = (int)I[r::L];
+            p.Atot = (int)I[r::Atot];
+            p.K = (int)I[r::K];
+            p.topk = (int)I[r::topk];
             EDGEDET_REQUIRE(p.L >= 1 && p.L <= 5, "retina_select: 1..5 levels");
             for (int l = 0; l < p.L; ++l) {
-                p.a0[l] = (int)I[6 + l];
-                p.na[l] = (int)I[11 + l];
+                p.a0[l] = (int)I[r::first0 + l];
+                p.na[l] = (int)I[r::count0 + l];
             }
-            p.img_h = o.f[0];
-            p.img_w = o.f[1];
-            p.score_thresh = o.f[2];
-            p.ckey = P<uint32_t>(o, 8);
-            p.cidx = P<int>(o, 9);
-            p.ccount = P<int>(o, 10);
-            p.chunk = (int)I[16];
-            p.nchunk = (int)I[17];
-            return retina_select_launch(p, seg_out(o, 3, (int)I[5]), s);
+            p.img_h = o.f[r::img_h];
+            p.img_w = o.f[r::img_w];
+            p.score_thresh = o.f[r::score_thresh];
+            p.ckey = P<uint32_t>(o, r::ckey);
+            p.cidx = P<int>(o, r::cidx);
+            p.ccount = P<int>(o, r::ccount);
+            p.chunk = (int)I[r::chunk];
+            p.nchunk = (int)I[r::nchunk];
+            return retina_select_launch(p, seg_out(o, r::records0, (int)I[r::kmax]), s);
         }
         case EDGEDET_OP_SSD_STEM: {
+            namespace r = rec::ssd_stem;
             StemParams p{};
-            p.x = P<const float>(o, 0);
-            p.w0 = P<const float>(o, 1);
-            p.b0 = P<const float>(o, 2);
-            p.wd = P<const float>(o, 3);
-            p.bd = P<const float>(o, 4);
-            p.w1 = P<const float>(o, 5);
-            p.b1 = P<const float>(o, 6);
-            p.y = P<float>(o, 7);
-            p.B = (int)I[0];
-            p.H = (int)I[1];
-            p.W = (int)I[2];
-            p.Ho = (int)I[3];
-            p.Wo = (int)I[4];
-            p.ld0 = (int)I[5];
-            p.ld1 = (int)I[6];
-            p.src = P<const float>(o, 8);  // the transform folded in: source image, its size and normalisation
-            p.src8 = P<const uint8_t>(o, 9);
-            p.H0 = (int)I[7];
-            p.W0 = (int)I[8];
+            p.x = P<const float>(o, r::x);
+            p.w0 = P<const float>(o, r::w0);
+            p.b0 = P<const float>(o, r::b0);
+            p.wd = P<const float>(o, r::wd);
+            p.bd = P<const float>(o, r::bd);
+            p.w1 = P<const float>(o, r::w1);
+            p.b1 = P<const float>(o, r::b1);
+            p.y = P<float>(o, r::y);
+            p.B = (int)I[r::B];
+            p.H = (int)I[r::H];
+            p.W = (int)I[r::W];
+            p.Ho = (int)I[r::Ho];
+            p.Wo = (int)I[r::Wo];
+            p.ld0 = (int)I[r::ld0];
+            p.ld1 = (int)I[r::ld1];
+            p.src = P<const float>(o, r::src);  // the transform folded in: source image, its size and normalisation
+            p.src8 = P<const uint8_t>(o, r::src8);
+            p.H0 = (int)I[r::H0];
+            p.W0 = (int)I[r::W0];
             for (int c = 0; c < 3; ++c) {
-                p.mean[c] = o.f[c];
-                p.stdv[c] = o.f[3 + c];
+                p.mean[c] = o.f[r::mean0 + c];
+                p.stdv[c] = o.f[r::std0 + c];
             }
             return ssd_stem_launch(p, s);
         }
         case EDGEDET_OP_RETINA_CLASS_NMS: {
+            namespace r = rec::retina_class_nms;
             RetinaNmsParams p{};
-            p.box = P<const f32x4>(o, 0);
-            p.score = P<const float>(o, 1);
-            p.label = P<const int>(o, 3);
-            p.count = P<const int>(o, 4);
-            p.L = (int)I[1];
-            p.kin = (int)I[2];
-            p.K = (int)I[3];
-            p.iou = make_iou_thr(o.d[0]);
-            return retina_class_nms_launch(p, (int)I[0], seg_out(o, 5, (int)I[4]), s);
+            p.box = P<const f32x4>(o, r::level0 + rec::seg::box);
+            p.score = P<const float>(o, r::level0 + rec::seg::score);
+            p.label = P<const int>(o, r::level0 + rec::seg::label);
+            p.count = P<const int>(o, r::level0 + rec::seg::count);
+            p.L = (int)I[r::L];
+            p.kin = (int)I[r::kin];
+            p.K = (int)I[r::K];
+            p.iou = make_iou_thr(o.d[r::iou]);
+            return retina_class_nms_launch(p, (int)I[r::B], seg_out(o, r::records0, (int)I[r::kmax]), s);
         }
         case EDGEDET_OP_SSD_POSTPROCESS: {
+            namespace r = rec::ssd_postprocess;
             SsdPostParams p{};
-            p.scores_t = P<const float>(o, 0);
-            p.boxes = P<const float>(o, 1);
-            p.pool_key = P<uint32_t>(o, 2);
-            p.pool_ref = P<int>(o, 3);
-            p.ratio = P<const float>(o, 4);
-            p.out_box = P<float>(o, 5);
-            p.out_score = P<float>(o, 6);
-            p.out_label = P<int64_t>(o, 7);
-            p.out_count = P<int>(o, 8);
-            p.B = (int)I[0];
-            p.A = (int)I[1];
-            p.NC = (int)I[2];
-            p.topk = (int)I[3];
-            p.N = (int)I[4];
-            p.select_wave = (int)I[5];
-            p.score_thresh = o.f[0];
-            p.iou = o.d[0];
+            p.scores_t = P<const float>(o, r::scores_t);
+            p.boxes = P<const float>(o, r::boxes);
+            p.pool_key = P<uint32_t>(o, r::pool_key);
+            p.pool_ref = P<int>(o, r::pool_ref);
+            p.ratio = P<const float>(o, r::ratio);
+            p.out_box = P<float>(o, r::out_box);
+            p.out_score = P<float>(o, r::out_score);
+            p.out_label = P<int64_t>(o, r::out_label);
+            p.out_count = P<int>(o, r::out_count);
+            p.B = (int)I[r::B];
+            p.A = (int)I[r::A];
+            p.NC = (int)I[r::NC];
+            p.topk = (int)I[r::topk];
+            p.N = (int)I[r::N];
+            p.select_wave = (int)I[r::select_wave];
+            p.score_thresh = o.f[r::score_thresh];
+            p.iou = o.d[r::iou];
             return ssd_postprocess_launch(p, s);
         }
         default:
@@ -540,20 +527,22 @@ static int64_t check_topology(const edgedet_op* ops, int64_t n) {
         const std::string at = "op " + std::to_string(k) + ": ";
         if (o.kind == EDGEDET_OP_FORK) {
             EDGEDET_REQUIRE(forked == 0, at + "fork while side lanes are open");
-            EDGEDET_REQUIRE(o.i[0] >= 1 && o.i[0] < EDGEDET_MAX_LANES, at + "fork: 1..3 side lanes");
-            forked = (int)o.i[0];
+            const int64_t lanes = o.i[rec::fork::lanes];
+            EDGEDET_REQUIRE(lanes >= 1 && lanes < EDGEDET_MAX_LANES, at + "fork: 1..3 side lanes");
+            forked = (int)lanes;
         } else if (o.kind == EDGEDET_OP_JOIN) {
-            EDGEDET_REQUIRE(o.i[0] >= 1 && o.i[0] < EDGEDET_MAX_LANES && o.i[0] == forked,
+            const int64_t lanes = o.i[rec::join::lanes];
+            EDGEDET_REQUIRE(lanes >= 1 && lanes < EDGEDET_MAX_LANES && lanes == forked,
                             at + "join: the forked side lanes");
             forked = 0;
         } else if (o.kind == EDGEDET_OP_WAIT) {
-            const int64_t a = o.i[0], b = o.i[1];
+            const int64_t a = o.i[rec::wait::waiter], b = o.i[rec::wait::waited];
             EDGEDET_REQUIRE(a >= 0 && b >= 0 && a != b && a <= forked && b <= forked,
                             at + "wait: two distinct forked lanes");
             ++waits;
         } else if (o.kind == EDGEDET_OP_GROUP) {
-            // the next i0 records: all CONV or all DWCONV, on the GROUP record's lane
-            const int64_t g = o.i[0], lane = o.i[EDGEDET_OP_LANE];
+            // the next `members` records: all CONV or all DWCONV, on the GROUP record's lane
+            const int64_t g = o.i[rec::group::members], lane = o.i[EDGEDET_OP_LANE];
             EDGEDET_REQUIRE(g >= 1 && g <= EDGEDET_MAX_GROUP && k + g < n, at + "group: 1..12 following records");
             EDGEDET_REQUIRE(lane >= 0 && lane < EDGEDET_MAX_LANES && (lane == 0 || lane <= forked),
                             at + "group on a lane that is not forked");
@@ -564,7 +553,7 @@ static int64_t check_topology(const edgedet_op* ops, int64_t n) {
                                 at + "group: members of one kind on the group's lane");
                 // one grouped launch runs one tile: run_group resolves member 0's requested tile
                 // for every member, so members requesting different tiles are refused here
-                EDGEDET_REQUIRE(kind != EDGEDET_OP_CONV || ops[j].i[23] == ops[k + 1].i[23],
+                EDGEDET_REQUIRE(kind != EDGEDET_OP_CONV || ops[j].i[rec::conv::tile] == ops[k + 1].i[rec::conv::tile],
                                 at + "group: CONV members requesting different tiles (i23)");
             }
             k += g;
@@ -589,7 +578,7 @@ static int run_group(const edgedet_op* m, int n, hipStream_t s) {
             ps[k] = conv_params(m[k]);
             EDGEDET_REQUIRE(ps[k].K == ps[k].KH * ps[k].KW * ps[k].Cin, "conv: K != KH*KW*Cin");
         }
-        rc = conv_group_launch(ps, n, (int)m[0].i[23], s);
+        rc = conv_group_launch(ps, n, (int)m[0].i[rec::conv::tile], s);
     } else {
         DwParams ps[EDGEDET_MAX_GROUP];
         for (int k = 0; k < n; ++k) ps[k] = dw_params(m[k]);
@@ -621,20 +610,21 @@ static int run_ops(const edgedet_op* ops, int64_t n, hipStream_t s) {
         int rc = 0;
         if (o.kind == EDGEDET_OP_FORK) {
             EDGEDET_CHECK_HIP(hipEventRecord(lanes->fork_ev, s));
-            for (int l = 1; l <= (int)o.i[0]; ++l)
+            for (int l = 1; l <= (int)o.i[rec::fork::lanes]; ++l)
                 EDGEDET_CHECK_HIP(hipStreamWaitEvent(lanes->side[l], lanes->fork_ev, 0));
         } else if (o.kind == EDGEDET_OP_JOIN) {
-            for (int l = 1; l <= (int)o.i[0]; ++l) {
+            for (int l = 1; l <= (int)o.i[rec::join::lanes]; ++l) {
                 EDGEDET_CHECK_HIP(hipEventRecord(lanes->join_ev[l], lanes->side[l]));
                 EDGEDET_CHECK_HIP(hipStreamWaitEvent(s, lanes->join_ev[l], 0));
             }
         } else if (o.kind == EDGEDET_OP_WAIT) {
             hipEvent_t e = lanes->wait_ev[(size_t)wait_k++];
-            EDGEDET_CHECK_HIP(hipEventRecord(e, lane_stream(o.i[1])));
-            EDGEDET_CHECK_HIP(hipStreamWaitEvent(lane_stream(o.i[0]), e, 0));
+            EDGEDET_CHECK_HIP(hipEventRecord(e, lane_stream(o.i[rec::wait::waited])));
+            EDGEDET_CHECK_HIP(hipStreamWaitEvent(lane_stream(o.i[rec::wait::waiter]), e, 0));
         } else if (o.kind == EDGEDET_OP_GROUP) {
-            rc = run_group(ops + k + 1, (int)o.i[0], lane_stream(o.i[EDGEDET_OP_LANE]));
-            k += o.i[0];
+            const int64_t g = o.i[rec::group::members];
+            rc = run_group(ops + k + 1, (int)g, lane_stream(o.i[EDGEDET_OP_LANE]));
+            k += g;
         } else {
             rc = run_op(o, lane_stream(o.i[EDGEDET_OP_LANE]));
         }
@@ -763,7 +753,7 @@ extern "C" int edgedet_conv_tile(const edgedet_op* op) {
     ConvParams p = conv_params(*op);
     const int rc = conv_prepare(p);
     if (rc) return rc;
-    return conv_resolve_tile(p, (int)op->i[23]);
+    return conv_resolve_tile(p, (int)op->i[rec::conv::tile]);
 }
 
 extern "C" const char* edgedet_last_error(void) { return get_error(); }

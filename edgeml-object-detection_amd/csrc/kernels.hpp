@@ -212,6 +212,19 @@ struct RetinaNmsParams {
 int gn_stats_launch(const GnParams& p, hipStream_t s);
 int retina_select_launch(const RetinaSelParams& P, SegOut out, hipStream_t s);
 int retina_class_nms_launch(const RetinaNmsParams& P, int B, SegOut out, hipStream_t s);
+// The conv tile ids that code outside conv_launch's switch refers to (conv.hip; that switch is the whole
+// table).  The numbers are frozen: data/conv_tiles_gfx950.json and the Python host use them.
+enum ConvTile : int {
+    TILE_AUTO = 0,                 // conv_resolve_tile chooses
+    TILE_X6B_256x128 = 25,         // bf16x6, 32-deep swizzled stages; takes the pre-split input (CONV p x3)
+    TILE_X6B_256x128_SPLITK = 26,  // the same, K in two halves accumulated with atomics into a zeroed y
+    TILE_X6B_128x128 = 29,
+    TILE_X6B_64x128 = 31,
+    TILE_PW_STREAM_WAVE = 34,      // streaming 1x1, one column block per wave, next block prefetched
+    TILE_PW_STREAM_WAVE_NOPF = 35, // the same without the prefetch
+    TILE_X6B_128x64 = 38,
+    TILE_X6B_128x256 = 39,         // one N tile for Cout = 256: each A panel read once
+};
 int conv_prepare(ConvParams& p);
 int conv_resolve_tile(const ConvParams& p, int tile);
 int conv_launch(ConvParams p, int tile, hipStream_t s);

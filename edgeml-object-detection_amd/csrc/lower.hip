@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "records.hpp"
 
 namespace edgedet {
 namespace lower {
@@ -392,7 +393,7 @@ struct Plan {
         OpRec o;
         o.kind = EDGEDET_OP_FORK;
         o.name = "fork";
-        o.i[0] = n;
+        o.i[rec::fork::lanes] = n;
         ops.push_back(o);
         forked = n;
     }
@@ -402,7 +403,7 @@ struct Plan {
         OpRec o;
         o.kind = EDGEDET_OP_JOIN;
         o.name = "join";
-        o.i[0] = forked;
+        o.i[rec::join::lanes] = forked;
         ops.push_back(o);
         forked = 0;
     }
@@ -422,13 +423,15 @@ static std::string conv_key(const OpRec& o) {
         auto it = o.i.find(k);
         return it == o.i.end() ? (int64_t)0 : it->second;
     };
-    const int lin = I(7) == 1 && I(8) == 1 && I(9) == 1 && I(10) == 0;
+    namespace r = rec::conv;
+    const int lin = I(r::KH) == 1 && I(r::KW) == 1 && I(r::stride) == 1 && I(r::pad) == 0;
     auto has = [&](int k) {
         auto it = o.p.find(k);
         return it != o.p.end() && it->second.kind != Ref::NONE;
     };
     std::string s;
-    const int64_t v[12] = {I(0), I(1), I(2), I(3), I(4), I(5), I(6), I(7), I(9), lin, has(6), has(7)};
+    const int64_t v[12] = {I(r::B),  I(r::H),    I(r::W),  I(r::Cin),    I(r::Ho), I(r::Wo),
+                           I(r::Cout), I(r::KH), I(r::stride), lin, has(r::w3), has(r::in_shift)};
     for (int j = 0; j < 12; ++j) s += (j ? "," : "") + std::to_string(v[j]);
     return s;
 }
@@ -455,53 +458,97 @@ static void conv_op(Plan& P, const ConvArgs& a) {
     const int64_t xp = a.x_pstride < 0 ? C : a.x_pstride;
     const int64_t yp = a.y_pstride < 0 ? a.cout : a.y_pstride;
     const int64_t rH = a.res_h < 0 ? Ho : a.res_h, rW = a.res_w < 0 ? Wo : a.res_w;
+    namespace r = rec::conv;
+    const bool bf16x6 = !env_is("EDGEDET_CONV_MATH", "f32", "bf16x6");
     OpRec o;
     o.kind = EDGEDET_OP_CONV;
     o.name = a.name;
-    const int64_t iv[25] = {B, H, W, C, Ho, Wo, a.cout, a.k, a.k, a.stride, a.pad, a.act, a.w.K, a.w.Kpad, xp, yp,
-                            a.cout, a.x_bstride < 0 ? H * W * xp : a.x_bstride,
-                            a.y_bstride < 0 ? Ho * Wo * yp : a.y_bstride, rH * rW * a.cout, a.y_off, rH, rW, a.tile,
-                            a.in_relu ? 1 : 0};
-    for (int j = 0; j < 25; ++j) o.i[j] = iv[j];
-    const bool bf16x6 = !env_is("EDGEDET_CONV_MATH", "f32", "bf16x6");
-    o.p[0] = a.x;
-    o.p[1] = Plan::wref(a.w.w);
-    o.p[2] = Plan::wref(a.w.b);
-    o.p[3] = a.y;
-    o.p[4] = a.res;
-    o.p[5] = a.in_scale;
-    o.p[6] = bf16x6 ? Plan::wsplit(a.w.w) : Ref();
-    o.p[7] = a.in_shift;
-    const bool w3 = o.p[6].kind != Ref::NONE;
+    o.i = {{r::B, B}, {r::H, H}, {r::W, W}, {r::Cin, C}, {r::Ho, Ho}, {r::Wo, Wo}, {r::Cout, a.cout},
+           {r::KH, a.k}, {r::KW, a.k}, {r::stride, a.stride}, {r::pad, a.pad}, {r::act, a.act},
+           {r::K, a.w.K}, {r::Kpad, a.w.Kpad}, {r::x_pstride, xp}, {r::y_pstride, yp}, {r::res_pstride, a.cout},
+           {r::x_bstride, a.x_bstride < 0 ? H * W * xp : a.x_bstride},
+           {r::y_bstride, a.y_bstride < 0 ? Ho * Wo * yp : a.y_bstride}, {r::res_bstride, rH * rW * a.cout},
+           {r::y_off, a.y_off}, {r::res_H, rH}, {r::res_W, rW}, {r::tile, a.tile}, {r::in_relu, a.in_relu ? 1 : 0}};
+    o.p = {{r::x, a.x}, {r::w, Plan::wref(a.w.w)}, {r::bias, Plan::wref(a.w.b)}, {r::y, a.y}, {r::res, a.res},
+           {r::in_scale, a.in_scale}, {r::w3, bf16x6 ? Plan::wsplit(a.w.w) : Ref()}, {r::in_shift, a.in_shift}};
+    const bool w3 = o.p[r::w3].kind != Ref::NONE;
+    int64_t& tile = o.i[r::tile];
     if (!a.tile && env_int("EDGEDET_CONV_TUNED", 1) == 1) {
         auto it = tile_table().find(conv_key(o));
-        if (it != tile_table().end() && it->second && (w3 || it->second < 20)) o.i[23] = it->second;
+        if (it != tile_table().end() && it->second && (w3 || it->second < 20)) tile = it->second;
     }
     // the Cout = 256 layers the table puts on 256 x 128 run the 128 x 256 tile: one N tile, so each A
     // panel is read once (FRCNN 362.6 / 362.5 -> 369.9 / 373.8 img/s in alternated runs; box head 3x3
     // 2.09 -> 1.88 ms in the conv microbench, profiles/r4c_conv39.txt); input-transformed layers keep
-    // 25 and its pre-split input (below)
+    // 256 x 128 and its pre-split input (below)
     const bool xf = a.in_scale.kind != Ref::NONE || a.in_shift.kind != Ref::NONE || a.in_relu;
-    if (o.i[23] == 25 && a.cout == 256 && !xf) o.i[23] = 39;
-    if (o.i[23] == 26) {
+    if (tile == TILE_X6B_256x128 && a.cout == 256 && !xf) tile = TILE_X6B_128x256;
+    if (tile == TILE_X6B_256x128_SPLITK) {  // split K accumulates into a zeroed y: only where that is the whole store
         const bool dense = yp == a.cout && a.y_off == 0 && (a.y_bstride < 0 || a.y_bstride == Ho * Wo * a.cout);
         if (a.act == 0 && a.res.kind == Ref::NONE && dense && w3) {
             OpRec m;
             m.kind = EDGEDET_OP_MEMSET;
             m.name = a.name + ".zero";
-            m.i[0] = B * Ho * Wo * a.cout * 4;
-            m.p[0] = a.y;
+            m.i[rec::mem_set::bytes] = B * Ho * Wo * a.cout * 4;
+            m.p[rec::mem_set::ptr] = a.y;
             P.add(m);
         } else {
-            o.i[23] = 25;
+            tile = TILE_X6B_256x128;
         }
     }
     // pre-split input planes only where an input transform is fused (GN / SE / ReLU on load): the split
     // pass then also takes the per-element transform out of the GEMM loop; for a plain input the extra
     // HBM pass measured slower (FRCNN 336 -> 313 img/s)
-    if (xf && w3 && C % 32 == 0 && (o.i[23] == 0 || o.i[23] == 25))
-        o.p[8] = P.ref(P.x3_scratch(3 * B * H * W * C + 32));
+    if (xf && w3 && C % 32 == 0 && (tile == TILE_AUTO || tile == TILE_X6B_256x128))
+        o.p[r::x3] = P.ref(P.x3_scratch(3 * B * H * W * C + 32));
     P.add(o);
+}
+
+// The five buffers of a record list (rec::seg order) into the pointer slots from `base`.
+static void set_records(const Plan& P, OpRec& o, int base, const int (&recs)[5]) {
+    for (int j = 0; j < 5; ++j) o.p[base + j] = P.ref(recs[j]);
+}
+
+// GeneralizedRCNNTransform: src [B,3,H,W] (float, or the uint8 bytes) -> y [B,Hp,Wp,4], resized to Ho x Wo.
+static void preprocess_op(Plan& P, Ref src, bool u8, Ref y, int64_t B, int64_t H, int64_t W, int64_t Ho, int64_t Wo,
+                          int64_t Hp, int64_t Wp, const std::array<float, 3>& mean, const std::array<float, 3>& stdv) {
+    namespace r = rec::preprocess;
+    OpRec o;
+    o.kind = EDGEDET_OP_PREPROCESS;
+    o.name = "transform";
+    o.i = {{r::B, B}, {r::H, H}, {r::W, W}, {r::Ho, Ho}, {r::Wo, Wo}, {r::Hp, Hp}, {r::Wp, Wp}};
+    o.p = {{u8 ? r::xu8 : r::x, src}, {r::y, y}};
+    for (int c = 0; c < 3; ++c) {
+        o.f[r::mean0 + c] = mean[(size_t)c];
+        o.f[r::std0 + c] = stdv[(size_t)c];
+    }
+    P.add(o);
+}
+
+// The next `members` records (all CONV or all DWCONV) as one grouped launch.
+static void group_op(Plan& P, const std::string& name, int64_t members) {
+    OpRec g;
+    g.kind = EDGEDET_OP_GROUP;
+    g.name = name;
+    g.i[rec::group::members] = members;
+    P.add(g);
+}
+
+// Per image: merge the S record lists (kmax each), sort by score, keep N, rescale by ratio (or none).
+static void merge_topk_op(Plan& P, const std::string& name, const int (&recs)[5], Ref ratio, Ref out_box, Ref out_score,
+                          Ref out_label, Ref out_count, int64_t B, int64_t S, int64_t kmax, int64_t N) {
+    namespace r = rec::merge_topk;
+    OpRec m;
+    m.kind = EDGEDET_OP_MERGE_TOPK;
+    m.name = name;
+    m.i = {{r::B, B}, {r::S, S}, {r::kmax, kmax}, {r::N, N}};
+    set_records(P, m, r::records0, recs);
+    m.p[r::ratio] = ratio;
+    m.p[r::out_box] = out_box;
+    m.p[r::out_score] = out_score;
+    m.p[r::out_label] = out_label;
+    m.p[r::out_count] = out_count;
+    P.add(m);
 }
 
 // ------------------------------------------------------------------------------------ SSDLite
@@ -601,7 +648,7 @@ class SSDLite {
     // one x6b tile for the grouped head 1x1 convs: 128 x 64 (the cls heads' 546 columns fill 9 N tiles
     // of 64 to 95 %, 5 of 128 to 85 %): the group alone 60.5 -> 51.3 us, SSD +0.8 % in alternated
     // runs against 64 x 128 (tile 31; 128 x 128: 68.6 us, +0.5 %), profiles/r6h_head_tile_ab.txt
-    static constexpr int HEAD_TILE = 38;
+    static constexpr int HEAD_TILE = TILE_X6B_128x64;
 
     SSDLite(const Config& c, Packer& pk) : cfg_(c), pk_(pk), blocks_(mnv3_blocks(c.reduced_tail)) {}
 
@@ -657,15 +704,7 @@ class SSDLite {
         Cur cur;
         if (!stem_fuse) {
             const int x = P.buf({B, S, S, 4}, 4, "pre" + sfx);
-            OpRec o;
-            o.kind = EDGEDET_OP_PREPROCESS;
-            o.name = "transform";
-            const int64_t iv[7] = {B, H, W, S, S, S, S};
-            for (int j = 0; j < 7; ++j) o.i[j] = iv[j];
-            o.p[u8 ? 2 : 0] = view(inp);
-            o.p[1] = P.ref(x);
-            for (int j = 0; j < 6; ++j) o.f[j] = 0.5f;
-            P.add(o);
+            preprocess_op(P, view(inp), u8, P.ref(x), B, H, W, S, S, S, S, {0.5f, 0.5f, 0.5f}, {0.5f, 0.5f, 0.5f});
             cur = Cur{P.ref(x), {B, S, S, 4}};
         }
 
@@ -710,13 +749,11 @@ class SSDLite {
             OpRec o;
             o.kind = EDGEDET_OP_DWCONV;
             o.name = prefix;
-            const int64_t iv[11] = {B, in.s[1], in.s[2], C, Ho, Wo, k, stride, pad, act, parts};
-            for (int j = 0; j < 11; ++j) o.i[j] = iv[j];
-            o.p[0] = in.x;
-            o.p[1] = Plan::wref(w.w);
-            o.p[2] = Plan::wref(w.b);
-            o.p[3] = P.ref(y);
-            o.p[4] = part >= 0 ? P.ref(part) : Ref();
+            namespace r = rec::dwconv;
+            o.i = {{r::B, B}, {r::H, in.s[1]}, {r::W, in.s[2]}, {r::C, C}, {r::Ho, Ho}, {r::Wo, Wo}, {r::K, k},
+                   {r::stride, stride}, {r::pad, pad}, {r::act, act}, {r::parts, parts}};
+            o.p = {{r::x, in.x}, {r::w, Plan::wref(w.w)}, {r::bias, Plan::wref(w.b)}, {r::y, P.ref(y)},
+                   {r::part, part >= 0 ? P.ref(part) : Ref()}};
             P.add(o);
             return DwOut{Cur{P.ref(y), ys}, part, parts};
         };
@@ -730,15 +767,11 @@ class SSDLite {
             OpRec o;
             o.kind = EDGEDET_OP_SE_FC;
             o.name = p;
-            const int64_t iv[5] = {B, C, sq, in.y.s[1] * in.y.s[2], in.parts};
-            for (int j = 0; j < 5; ++j) o.i[j] = iv[j];
-            o.p[0] = P.ref(in.part);
-            o.p[1] = Plan::wref(w1);
-            o.p[2] = Plan::wref(b1);
-            o.p[3] = Plan::wref(w2t);
-            o.p[4] = Plan::wref(b2);
-            o.p[5] = P.ref(scale);
-            o.p[6] = P.ref(hidden);
+            namespace r = rec::se_fc;
+            o.i = {{r::B, B}, {r::C, C}, {r::S, sq}, {r::HW, in.y.s[1] * in.y.s[2]}, {r::parts, in.parts}};
+            o.p = {{r::part, P.ref(in.part)}, {r::w1, Plan::wref(w1)}, {r::b1, Plan::wref(b1)},
+                   {r::w2t, Plan::wref(w2t)}, {r::b2, Plan::wref(b2)}, {r::scale, P.ref(scale)},
+                   {r::hidden, P.ref(hidden)}};
             P.add(o);
             return P.ref(scale);
         };
@@ -753,17 +786,12 @@ class SSDLite {
             OpRec o;
             o.kind = EDGEDET_OP_MBCONV;
             o.name = pf.pe.substr(0, pf.pe.rfind('.'));
-            const int64_t iv[15] = {B, in.s[1], in.s[2], b.cin, b.exp, b.cout, Ho, Wo, b.k, b.stride, pad, b.act,
-                                    w1.Kpad, w2.Kpad, (b.stride == 1 && b.cin == b.cout) ? 1 : 0};
-            for (int j = 0; j < 15; ++j) o.i[j] = iv[j];
-            o.p[0] = in.x;
-            o.p[1] = Plan::wref(w1.w);
-            o.p[2] = Plan::wref(w1.b);
-            o.p[3] = Plan::wref(wd.w);
-            o.p[4] = Plan::wref(wd.b);
-            o.p[5] = Plan::wref(w2.w);
-            o.p[6] = Plan::wref(w2.b);
-            o.p[7] = P.ref(y);
+            namespace r = rec::mbconv;
+            o.i = {{r::B, B}, {r::H, in.s[1]}, {r::W, in.s[2]}, {r::Cin, b.cin}, {r::Cexp, b.exp}, {r::Cout, b.cout},
+                   {r::Ho, Ho}, {r::Wo, Wo}, {r::K, b.k}, {r::stride, b.stride}, {r::pad, pad}, {r::act, b.act},
+                   {r::ld1, w1.Kpad}, {r::ld2, w2.Kpad}, {r::residual, (b.stride == 1 && b.cin == b.cout) ? 1 : 0}};
+            o.p = {{r::x, in.x}, {r::w1, Plan::wref(w1.w)}, {r::b1, Plan::wref(w1.b)}, {r::wd, Plan::wref(wd.w)},
+                   {r::bd, Plan::wref(wd.b)}, {r::w2, Plan::wref(w2.w)}, {r::b2, Plan::wref(w2.b)}, {r::y, P.ref(y)}};
             P.add(o);
             return Cur{P.ref(y), ys};
         };
@@ -794,17 +822,14 @@ class SSDLite {
             OpRec o;
             o.kind = EDGEDET_OP_SSD_STEM;
             o.name = "transform+backbone.features.0.0+0.1";
-            const int64_t iv[9] = {B, S, S, Ho, Wo, w0.Kpad, w1.Kpad, H, W};
-            for (int j = 0; j < 9; ++j) o.i[j] = iv[j];
-            o.p[u8 ? 9 : 8] = view(inp);  // the source image; the transform runs in the stem's loads
-            for (int j = 0; j < 6; ++j) o.f[j] = 0.5f;
-            o.p[1] = Plan::wref(w0.w);
-            o.p[2] = Plan::wref(w0.b);
-            o.p[3] = Plan::wref(wd.w);
-            o.p[4] = Plan::wref(wd.b);
-            o.p[5] = Plan::wref(w1.w);
-            o.p[6] = Plan::wref(w1.b);
-            o.p[7] = P.ref(y);
+            namespace r = rec::ssd_stem;
+            o.i = {{r::B, B}, {r::H, S}, {r::W, S}, {r::Ho, Ho}, {r::Wo, Wo}, {r::ld0, w0.Kpad}, {r::ld1, w1.Kpad},
+                   {r::H0, H}, {r::W0, W}};
+            // src / src8: the source image; the transform runs in the stem's loads
+            o.p = {{u8 ? r::src8 : r::src, view(inp)}, {r::w0, Plan::wref(w0.w)}, {r::b0, Plan::wref(w0.b)},
+                   {r::wd, Plan::wref(wd.w)}, {r::bd, Plan::wref(wd.b)}, {r::w1, Plan::wref(w1.w)},
+                   {r::b1, Plan::wref(w1.b)}, {r::y, P.ref(y)}};
+            for (int c = 0; c < 3; ++c) o.f[r::mean0 + c] = o.f[r::std0 + c] = 0.5f;
             P.add(o);
             cur = Cur{P.ref(y), ys};
             first = 1;
@@ -869,17 +894,10 @@ class SSDLite {
             off += f.s[1] * f.s[2] * 6;
         }
         const int ng = (int)hops.size();
-        auto group = [&](const std::string& name) {
-            OpRec g;
-            g.kind = EDGEDET_OP_GROUP;
-            g.name = name + sfx;
-            g.i[0] = ng;
-            P.add(g);
-        };
         std::vector<Cur> hdw;
-        group("head.depthwise");
+        group_op(P, "head.depthwise" + sfx, ng);
         for (auto& h : hops) hdw.push_back(dw(*h.f, h.p + ".0", 3, 1, A_R6, false).y);
-        group("head.pointwise");
+        group_op(P, "head.pointwise" + sfx, ng);
         for (int k = 0; k < ng; ++k) {
             const HeadOp& h = hops[(size_t)k];
             const Cur& f = *h.f;
@@ -920,16 +938,11 @@ class SSDLite {
             OpRec o;
             o.kind = EDGEDET_OP_SSD_SCORES;
             o.name = "postprocess.scores" + sfx;
-            o.i[0] = B;
-            o.i[1] = A;
-            o.i[2] = NC;
-            o.p[0] = view(sh.cls);
-            o.p[1] = view(sh.reg);
-            o.p[2] = P.ref(sh.anchors);
-            o.p[3] = view(sh.scores_t);
-            o.p[4] = view(sh.boxes);
-            o.f[0] = (float)S;
-            o.f[1] = (float)S;
+            namespace r = rec::ssd_scores;
+            o.i = {{r::B, B}, {r::A, A}, {r::NC, NC}};
+            o.p = {{r::logits, view(sh.cls)}, {r::reg, view(sh.reg)}, {r::anchors, P.ref(sh.anchors)},
+                   {r::scores_t, view(sh.scores_t)}, {r::boxes, view(sh.boxes)}};
+            o.f = {{r::img_h, (float)S}, {r::img_w, (float)S}};
             P.add(o);
         }
         const int64_t NS = NC - 1, KM = TOPK;
@@ -941,56 +954,31 @@ class SSDLite {
             OpRec o;
             o.kind = EDGEDET_OP_SSD_POSTPROCESS;
             o.name = "postprocess.nms" + sfx;
-            const int64_t iv[5] = {B, A, NC, KM, DETS};
-            for (int j = 0; j < 5; ++j) o.i[j] = iv[j];
-            o.i[5] = 0;  // class selection: the four-wave block form (1: the one-wave form, unit tests)
-            o.p[0] = view(sh.scores_t);
-            o.p[1] = view(sh.boxes);
-            o.p[2] = P.ref(pk);
-            o.p[3] = P.ref(pr);
-            o.p[4] = view(sh.ratio);
-            o.p[5] = view(sh.ob);
-            o.p[6] = view(sh.os);
-            o.p[7] = view(sh.ol);
-            o.p[8] = view(sh.oc);
-            o.f[0] = (float)SCORE;
-            o.d[0] = NMS;
+            namespace r = rec::ssd_postprocess;
+            // select_wave 0: the four-wave block form of the class selection (1: the one-wave form, unit tests)
+            o.i = {{r::B, B}, {r::A, A}, {r::NC, NC}, {r::topk, KM}, {r::N, DETS}, {r::select_wave, 0}};
+            o.p = {{r::scores_t, view(sh.scores_t)}, {r::boxes, view(sh.boxes)}, {r::pool_key, P.ref(pk)},
+                   {r::pool_ref, P.ref(pr)}, {r::ratio, view(sh.ratio)}, {r::out_box, view(sh.ob)},
+                   {r::out_score, view(sh.os)}, {r::out_label, view(sh.ol)}, {r::out_count, view(sh.oc)}};
+            o.f[r::score_thresh] = (float)SCORE;
+            o.d[r::iou] = NMS;
             P.add(o);
         } else {
-            const int rb = P.buf({B, NS, KM, 4}, 4, "rec.box" + sfx), rs = P.buf({B, NS, KM}, 4, "rec.score" + sfx);
-            const int rt = P.buf({B, NS, KM}, I32, "rec.tb" + sfx), rl = P.buf({B, NS, KM}, I32, "rec.label" + sfx);
-            const int rc = P.buf({B, NS}, I32, "rec.count" + sfx);
+            const int recs[5] = {P.buf({B, NS, KM, 4}, 4, "rec.box" + sfx), P.buf({B, NS, KM}, 4, "rec.score" + sfx),
+                                 P.buf({B, NS, KM}, I32, "rec.tb" + sfx), P.buf({B, NS, KM}, I32, "rec.label" + sfx),
+                                 P.buf({B, NS}, I32, "rec.count" + sfx)};
             OpRec o;
             o.kind = EDGEDET_OP_SSD_CLASS_NMS;
             o.name = "postprocess.class_nms" + sfx;
-            const int64_t iv[5] = {B, A, NC, TOPK, KM};
-            for (int j = 0; j < 5; ++j) o.i[j] = iv[j];
-            o.p[0] = view(sh.scores_t);
-            o.p[1] = view(sh.boxes);
-            o.p[2] = P.ref(rb);
-            o.p[3] = P.ref(rs);
-            o.p[4] = P.ref(rt);
-            o.p[5] = P.ref(rl);
-            o.p[6] = P.ref(rc);
-            o.f[0] = (float)SCORE;
-            o.d[0] = NMS;
+            namespace r = rec::ssd_class_nms;
+            o.i = {{r::B, B}, {r::A, A}, {r::NC, NC}, {r::topk, TOPK}, {r::kmax, KM}};
+            o.p = {{r::scores_t, view(sh.scores_t)}, {r::boxes, view(sh.boxes)}};
+            set_records(P, o, r::records0, recs);
+            o.f[r::score_thresh] = (float)SCORE;
+            o.d[r::iou] = NMS;
             P.add(o);
-            OpRec m;
-            m.kind = EDGEDET_OP_MERGE_TOPK;
-            m.name = "postprocess.merge" + sfx;
-            const int64_t mv[4] = {B, NS, KM, DETS};
-            for (int j = 0; j < 4; ++j) m.i[j] = mv[j];
-            m.p[0] = P.ref(rb);
-            m.p[1] = P.ref(rs);
-            m.p[2] = P.ref(rt);
-            m.p[3] = P.ref(rl);
-            m.p[4] = P.ref(rc);
-            m.p[5] = view(sh.ratio);
-            m.p[6] = view(sh.ob);
-            m.p[7] = view(sh.os);
-            m.p[8] = view(sh.ol);
-            m.p[9] = view(sh.oc);
-            P.add(m);
+            merge_topk_op(P, "postprocess.merge" + sfx, recs, view(sh.ratio), view(sh.ob), view(sh.os), view(sh.ol),
+                          view(sh.oc), B, NS, KM, DETS);
         }
     }
 
@@ -1132,10 +1120,10 @@ class ResNetFPN {
         OpRec o;
         o.kind = EDGEDET_OP_MAXPOOL;
         o.name = name;
-        const int64_t iv[9] = {in.s[0], in.s[1], in.s[2], in.s[3], Ho_, Wo_, k, stride, pad};
-        for (int j = 0; j < 9; ++j) o.i[j] = iv[j];
-        o.p[0] = in.x;
-        o.p[1] = P.ref(y);
+        namespace r = rec::maxpool;
+        o.i = {{r::B, in.s[0]}, {r::H, in.s[1]}, {r::W, in.s[2]}, {r::C, in.s[3]}, {r::Ho, Ho_}, {r::Wo, Wo_},
+               {r::K, k}, {r::stride, stride}, {r::pad, pad}};
+        o.p = {{r::x, in.x}, {r::y, P.ref(y)}};
         P.add(o);
         return Cur{P.ref(y), ys};
     }
@@ -1151,21 +1139,8 @@ class ResNetFPN {
         r.Wp = (r.Wo + DIV - 1) / DIV * DIV;
         r.inp = P.buf({B, 3, H, W}, u8 ? 1 : 4, "images");
         const int x = P.buf({B, r.Hp, r.Wp, 4}, 4, "pre");
-        {
-            OpRec o;
-            o.kind = EDGEDET_OP_PREPROCESS;
-            o.name = "transform";
-            const int64_t iv[7] = {B, H, W, r.Ho, r.Wo, r.Hp, r.Wp};
-            for (int j = 0; j < 7; ++j) o.i[j] = iv[j];
-            o.p[u8 ? 2 : 0] = P.ref(r.inp);
-            o.p[1] = P.ref(x);
-            const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-            for (int j = 0; j < 3; ++j) {
-                o.f[j] = mean[j];
-                o.f[3 + j] = stdv[j];
-            }
-            P.add(o);
-        }
+        preprocess_op(P, P.ref(r.inp), u8, P.ref(x), B, H, W, r.Ho, r.Wo, r.Hp, r.Wp, {0.485f, 0.456f, 0.406f},
+                      {0.229f, 0.224f, 0.225f});
         Cur cur{P.ref(x), {B, r.Hp, r.Wp, 4}};
         const std::string pb = "backbone.body.";
         {
@@ -1235,7 +1210,7 @@ static std::vector<float> grid_anchors(int gh, int gw, int Hp, int Wp, const std
 class FasterRCNN : public ResNetFPN {
   public:
     static constexpr int RPN_PRE = 1000, RPN_POST = 1000, BOX_DETS = 100;
-    static constexpr int RPN_TILE = 39;  // the grouped RPN head 3x3 convs (Cout = 256): 128 x 256
+    static constexpr int RPN_TILE = TILE_X6B_128x256;  // the grouped RPN head 3x3 convs (Cout = 256)
     static constexpr int RPN_CHUNK = 8192;  // anchors per chunk of the chunked RPN top-k
     static constexpr double RPN_NMS = 0.7, RPN_MIN = 1e-3, RPN_SCORE = 0.0, BOX_SCORE = 0.05, BOX_NMS = 0.5,
                             BOX_MIN = 1e-2;
@@ -1287,16 +1262,9 @@ class FasterRCNN : public ResNetFPN {
         // the big level's tail instead of running as eight latency-bound launches after it (round 3 ran
         // the levels one after another on the caller stream; on four stream lanes was 0.75 % slower).
         const int L5 = (int)outs.size();
-        auto rpn_group = [&](const std::string& name) {
-            OpRec g;
-            g.kind = EDGEDET_OP_GROUP;
-            g.name = name;
-            g.i[0] = L5;
-            P.add(g);
-        };
         const bool grouped = !env_is("EDGEDET_CONV_MATH", "f32", "bf16x6");  // grouped launches: bf16x6 tiles
         std::vector<Cur> t0s, t1s;
-        if (grouped) rpn_group("rpn.head.conv.0");
+        if (grouped) group_op(P, "rpn.head.conv.0", L5);
         for (int lvl = 0; lvl < L5; ++lvl) {
             COpt o;
             o.bias_key = "rpn.head.conv.0.0.bias";
@@ -1304,7 +1272,7 @@ class FasterRCNN : public ResNetFPN {
             o.tile = grouped ? RPN_TILE : 0;
             t0s.push_back(conv(P, outs[(size_t)lvl], "rpn.head.conv.0.0.weight", 256, 3, 1, A_RE, o));
         }
-        if (grouped) rpn_group("rpn.head.conv.1");
+        if (grouped) group_op(P, "rpn.head.conv.1", L5);
         for (int lvl = 0; lvl < L5; ++lvl) {
             COpt o;
             o.bias_key = "rpn.head.conv.1.0.bias";
@@ -1328,82 +1296,66 @@ class FasterRCNN : public ResNetFPN {
         }
         const int L = (int)outs.size();
         const int KM = RPN_PRE;
-        const int rb = P.buf({B, L, KM, 4}, 4, "rpn.rec.box"), rs = P.buf({B, L, KM}, 4, "rpn.rec.score");
-        const int rt = P.buf({B, L, KM}, I32, "rpn.rec.tb"), rl = P.buf({B, L, KM}, I32, "rpn.rec.lvl");
-        const int rc = P.buf({B, L}, I32, "rpn.rec.count");
+        const int recs[5] = {P.buf({B, L, KM, 4}, 4, "rpn.rec.box"), P.buf({B, L, KM}, 4, "rpn.rec.score"),
+                             P.buf({B, L, KM}, I32, "rpn.rec.tb"), P.buf({B, L, KM}, I32, "rpn.rec.lvl"),
+                             P.buf({B, L}, I32, "rpn.rec.count")};
         {
+            namespace r = rec::rpn_level_nms;
             OpRec o;
             o.kind = EDGEDET_OP_RPN_LEVEL_NMS;
             o.name = "rpn.filter_proposals";
-            const int64_t iv[6] = {B, L, 0, Aa, RPN_PRE, KM};
-            for (int j = 0; j < 6; ++j) o.i[j] = iv[j];
-            for (int l = 0; l < L; ++l) {
-                o.i[6 + l] = (int64_t)grids[(size_t)l].first * grids[(size_t)l].second * Aa;
-                o.p[l] = heads[(size_t)l].first;
-                o.p[15 + l] = heads[(size_t)l].second;
-                o.p[5 + l] = P.ref(anchor_bufs[(size_t)l]);
-            }
-            const int recs[5] = {rb, rs, rt, rl, rc};
-            for (int j = 0; j < 5; ++j) o.p[10 + j] = P.ref(recs[j]);
-            o.f[0] = (float)Ho;
-            o.f[1] = (float)Wo;
-            o.f[2] = (float)RPN_MIN;
-            o.f[3] = (float)RPN_SCORE;
-            o.d[0] = RPN_NMS;
-            // chunked top-k: 8,192 anchors per chunk (P2 of an 800 x 800 image: 15 chunks per image)
+            o.i = {{r::B, B}, {r::nlevels, L}, {r::ld, 0}, {r::A, Aa}, {r::topk, RPN_PRE}, {r::kmax, KM}};
             int64_t nmax = 0;
-            for (int l = 0; l < L; ++l) nmax = std::max<int64_t>(nmax, o.i[6 + l]);
+            for (int l = 0; l < L; ++l) {
+                const int64_t n = (int64_t)grids[(size_t)l].first * grids[(size_t)l].second * Aa;
+                nmax = std::max(nmax, n);
+                o.i[r::n0 + l] = n;
+                o.p[r::obj0 + l] = heads[(size_t)l].first;
+                o.p[r::deltas0 + l] = heads[(size_t)l].second;
+                o.p[r::anchors0 + l] = P.ref(anchor_bufs[(size_t)l]);
+            }
+            set_records(P, o, r::records0, recs);
+            o.f = {{r::img_h, (float)Ho}, {r::img_w, (float)Wo}, {r::min_size, (float)RPN_MIN},
+                   {r::score_thresh, (float)RPN_SCORE}};
+            o.d[r::iou] = RPN_NMS;
+            // chunked top-k: 8,192 anchors per chunk (P2 of an 800 x 800 image: 15 chunks per image)
             const int64_t chunk = RPN_CHUNK, nch = (nmax + chunk - 1) / chunk;
-            o.p[20] = P.ref(P.buf({B, L, nch, 1024}, I32, "rpn.chunk.key"));
-            o.p[21] = P.ref(P.buf({B, L, nch, 1024}, I32, "rpn.chunk.idx"));
-            o.p[22] = P.ref(P.buf({B, L, nch}, I32, "rpn.chunk.count"));
-            o.i[16] = chunk;
-            o.i[17] = nch;
+            o.p[r::ckey] = P.ref(P.buf({B, L, nch, 1024}, I32, "rpn.chunk.key"));
+            o.p[r::cidx] = P.ref(P.buf({B, L, nch, 1024}, I32, "rpn.chunk.idx"));
+            o.p[r::ccount] = P.ref(P.buf({B, L, nch}, I32, "rpn.chunk.count"));
+            o.i[r::chunk] = chunk;
+            o.i[r::nchunk] = nch;
             // split NMS (selection / IoU mask over many workgroups / scan): EDGEDET_RPN_SPLIT=0 keeps one
             // workgroup per (level, image) for the whole segment
             if (env_int("EDGEDET_RPN_SPLIT", 1))
-                o.p[23] = P.ref(P.buf({rpn_split_bytes((int64_t)B * L)}, 1, "rpn.nms.split"));
+                o.p[r::split] = P.ref(P.buf({rpn_split_bytes((int64_t)B * L)}, 1, "rpn.nms.split"));
             P.add(o);
         }
         const int R = RPN_POST;
         const int props = P.buf({B, R, 4}, 4, "proposals"), pscore = P.buf({B, R}, 4, "proposal_scores");
         const int pcount = P.buf({B}, I32, "proposal_count");
-        {
-            OpRec o;
-            o.kind = EDGEDET_OP_MERGE_TOPK;
-            o.name = "rpn.post_nms_top_n";
-            const int64_t iv[4] = {B, L, KM, R};
-            for (int j = 0; j < 4; ++j) o.i[j] = iv[j];
-            const int recs[5] = {rb, rs, rt, rl, rc};
-            for (int j = 0; j < 5; ++j) o.p[j] = P.ref(recs[j]);
-            o.p[5] = Ref();
-            o.p[6] = P.ref(props);
-            o.p[7] = P.ref(pscore);
-            o.p[8] = Ref();
-            o.p[9] = P.ref(pcount);
-            P.add(o);
-        }
+        merge_topk_op(P, "rpn.post_nms_top_n", recs, Ref(), P.ref(props), P.ref(pscore), Ref(), P.ref(pcount), B, L, KM,
+                      R);
 
         // ---- MultiScaleRoIAlign
         const int C = 256;
         const int roi = P.buf({(int64_t)B * R, 7, 7, C}, 4, "box_roi_pool");
         {
+            namespace r = rec::roi_align;
             OpRec o;
             o.kind = EDGEDET_OP_ROI_ALIGN;
             o.name = "roi_heads.box_roi_pool";
-            const int64_t iv[11] = {1, (int64_t)B * R, R, B, C, 7, 7, 2, 4, 2, 5};
-            for (int j = 0; j < 11; ++j) o.i[j] = iv[j];
-            o.p[4] = P.ref(props);
-            o.p[5] = P.ref(pcount);
-            o.p[6] = P.ref(roi);
+            o.i = {{r::mode, 1}, {r::R, (int64_t)B * R}, {r::RMAX, R}, {r::B, B}, {r::C, C}, {r::PH, 7}, {r::PW, 7},
+                   {r::sr, 2}, {r::nlevels, 4}, {r::k_min, 2}, {r::k_max, 5}};
+            o.p = {{r::rois, P.ref(props)}, {r::counts, P.ref(pcount)}, {r::out, P.ref(roi)}};
             for (int l = 0; l < 4; ++l) {
                 const int fh = (int)outs[(size_t)l].s[1], fw = (int)outs[(size_t)l].s[2];
-                o.i[11 + l] = fh;
-                o.i[15 + l] = fw;
-                o.p[l] = outs[(size_t)l].x;
+                o.i[r::H0 + l] = fh;
+                o.i[r::W0 + l] = fw;
+                o.p[r::feat0 + l] = outs[(size_t)l].x;
                 // MultiScaleRoIAlign._infer_scale: 2 ** round(log2(feat / image)) in float32
-                const float r = (float)((double)fh / (double)Ho);
-                o.f[l] = (float)std::pow(2.0, (double)std::nearbyint(std::log2(r)));
+                const float ratio = (float)((double)fh / (double)Ho);
+                o.f[r::scale0 + l] = (float)std::pow(2.0, (double)std::nearbyint(std::log2(ratio)));
             }
             P.add(o);
         }
@@ -1445,37 +1397,33 @@ class FasterRCNN : public ResNetFPN {
             // ---- RoIHeads.postprocess_detections
             const int scores = P.buf({B, R, NC}, 4, "box_scores");
             const int bxs = P.buf({B, R, NC, 4}, 4, "box_decoded");
-            OpRec o;
-            o.kind = EDGEDET_OP_BOX_SCORES;
-            o.name = "roi_heads.scores_decode";
-            const int64_t iv[6] = {LD, B, R, NC, 4 * NC, 0};
-            for (int j = 0; j < 6; ++j) o.i[j] = iv[j];
-            o.p[0] = P.ref(pred);
-            o.p[1] = P.ref(props);
-            o.p[2] = P.ref(pcount);
-            o.p[3] = P.ref(scores);
-            o.p[4] = P.ref(bxs);
-            o.f[0] = (float)Ho;
-            o.f[1] = (float)Wo;
-            P.add(o);
+            {
+                namespace r = rec::box_scores;
+                OpRec o;
+                o.kind = EDGEDET_OP_BOX_SCORES;
+                o.name = "roi_heads.scores_decode";
+                o.i = {{r::ld, LD}, {r::B, B}, {r::R, R}, {r::NC, NC}, {r::cls_off, 4 * NC}, {r::delta_off, 0}};
+                o.p = {{r::pred, P.ref(pred)}, {r::props, P.ref(props)}, {r::counts, P.ref(pcount)},
+                       {r::scores, P.ref(scores)}, {r::boxes, P.ref(bxs)}};
+                o.f = {{r::img_h, (float)Ho}, {r::img_w, (float)Wo}};
+                P.add(o);
+            }
             const int NS = NC - 1;
-            const int b0 = P.buf({B, NS, R, 4}, 4, "box.rec.box"), b1 = P.buf({B, NS, R}, 4, "box.rec.score");
-            const int b2 = P.buf({B, NS, R}, I32, "box.rec.tb"), b3 = P.buf({B, NS, R}, I32, "box.rec.lbl");
-            const int b4 = P.buf({B, NS}, I32, "box.rec.count");
-            OpRec n;
-            n.kind = EDGEDET_OP_BOX_CLASS_NMS;
-            n.name = "roi_heads.class_nms";
-            const int64_t nv[4] = {B, R, NC, R};
-            for (int j = 0; j < 4; ++j) n.i[j] = nv[j];
-            n.p[0] = P.ref(scores);
-            n.p[1] = P.ref(bxs);
-            n.p[2] = P.ref(pcount);
-            const int brec[5] = {b0, b1, b2, b3, b4};
-            for (int j = 0; j < 5; ++j) n.p[3 + j] = P.ref(brec[j]);
-            n.f[0] = (float)BOX_SCORE;
-            n.f[1] = (float)BOX_MIN;
-            n.d[0] = BOX_NMS;
-            P.add(n);
+            const int brec[5] = {P.buf({B, NS, R, 4}, 4, "box.rec.box"), P.buf({B, NS, R}, 4, "box.rec.score"),
+                                 P.buf({B, NS, R}, I32, "box.rec.tb"), P.buf({B, NS, R}, I32, "box.rec.lbl"),
+                                 P.buf({B, NS}, I32, "box.rec.count")};
+            {
+                namespace r = rec::box_class_nms;
+                OpRec n;
+                n.kind = EDGEDET_OP_BOX_CLASS_NMS;
+                n.name = "roi_heads.class_nms";
+                n.i = {{r::B, B}, {r::R, R}, {r::NC, NC}, {r::kmax, R}};
+                n.p = {{r::scores, P.ref(scores)}, {r::boxes, P.ref(bxs)}, {r::counts, P.ref(pcount)}};
+                set_records(P, n, r::records0, brec);
+                n.f = {{r::score_thresh, (float)BOX_SCORE}, {r::min_size, (float)BOX_MIN}};
+                n.d[r::iou] = BOX_NMS;
+                P.add(n);
+            }
             std::vector<float> ratio;
             for (int b = 0; b < B; ++b) {
                 ratio.push_back((float)W / (float)Wo);
@@ -1487,18 +1435,8 @@ class FasterRCNN : public ResNetFPN {
             P.out_score = P.buf({B, N}, 4, "out.scores");
             P.out_label = P.buf({B, N}, 8, "out.labels");
             P.out_count = P.buf({B}, I32, "out.count");
-            OpRec m;
-            m.kind = EDGEDET_OP_MERGE_TOPK;
-            m.name = "roi_heads.detections_per_img";
-            const int64_t mv[4] = {B, NS, R, N};
-            for (int j = 0; j < 4; ++j) m.i[j] = mv[j];
-            for (int j = 0; j < 5; ++j) m.p[j] = P.ref(brec[j]);
-            m.p[5] = P.ref(rbuf);
-            m.p[6] = P.ref(P.out_box);
-            m.p[7] = P.ref(P.out_score);
-            m.p[8] = P.ref(P.out_label);
-            m.p[9] = P.ref(P.out_count);
-            P.add(m);
+            merge_topk_op(P, "roi_heads.detections_per_img", brec, P.ref(rbuf), P.ref(P.out_box), P.ref(P.out_score),
+                          P.ref(P.out_label), P.ref(P.out_count), B, NS, R, N);
         }
         P.input = bd.inp;
         P.dets = BOX_DETS;
@@ -1634,16 +1572,11 @@ class RetinaNet : public ResNetFPN {
                     OpRec s;
                     s.kind = EDGEDET_OP_GN_STATS;
                     s.name = q + "1" + at;
-                    s.i[0] = B;
-                    s.i[1] = hw;
-                    s.i[2] = C;
-                    s.i[3] = GROUPS;
-                    s.p[0] = t.x;
-                    s.p[1] = Plan::wref(g);
-                    s.p[2] = Plan::wref(b);
-                    s.p[3] = P.ref(scb);
-                    s.p[4] = P.ref(shb);
-                    s.f[0] = (float)GN_EPS;
+                    namespace r = rec::gn_stats;
+                    s.i = {{r::B, B}, {r::HW, hw}, {r::C, C}, {r::G, GROUPS}};
+                    s.p = {{r::x, t.x}, {r::gamma, Plan::wref(g)}, {r::beta, Plan::wref(b)}, {r::scale, P.ref(scb)},
+                           {r::shift, P.ref(shb)}};
+                    s.f[r::eps] = (float)GN_EPS;
                     P.add(s);
                     sc = P.ref(scb);
                     sh = P.ref(shb);
@@ -1683,27 +1616,20 @@ class RetinaNet : public ResNetFPN {
         const int ci = P.buf({B, L, nchunk, 1024}, I32, "retina.chunk.idx");
         const int cc = P.buf({B, L, nchunk}, I32, "retina.chunk.count");
         {
+            namespace r = rec::retina_select;
             OpRec o;
             o.kind = EDGEDET_OP_RETINA_SELECT;
             o.name = "retina.select_topk";
-            const int64_t iv[6] = {B, L, Atot, K, TOPK, KM};
-            for (int j = 0; j < 6; ++j) o.i[j] = iv[j];
-            o.i[16] = SELECT_CHUNK;
-            o.i[17] = nchunk;
+            o.i = {{r::B, B}, {r::L, L}, {r::Atot, Atot}, {r::K, K}, {r::topk, TOPK}, {r::kmax, KM},
+                   {r::chunk, SELECT_CHUNK}, {r::nchunk, nchunk}};
             for (int l = 0; l < L; ++l) {
-                o.i[6 + l] = a0[(size_t)l];
-                o.i[11 + l] = na[(size_t)l];
+                o.i[r::first0 + l] = a0[(size_t)l];
+                o.i[r::count0 + l] = na[(size_t)l];
             }
-            o.p[0] = P.ref(cls);
-            o.p[1] = P.ref(reg);
-            o.p[2] = P.ref(anc);
-            for (int j = 0; j < 5; ++j) o.p[3 + j] = P.ref(lrec[j]);
-            o.p[8] = P.ref(ck);
-            o.p[9] = P.ref(ci);
-            o.p[10] = P.ref(cc);
-            o.f[0] = (float)Ho;
-            o.f[1] = (float)Wo;
-            o.f[2] = (float)SCORE;
+            o.p = {{r::logits, P.ref(cls)}, {r::deltas, P.ref(reg)}, {r::anchors, P.ref(anc)}, {r::ckey, P.ref(ck)},
+                   {r::cidx, P.ref(ci)}, {r::ccount, P.ref(cc)}};
+            set_records(P, o, r::records0, lrec);
+            o.f = {{r::img_h, (float)Ho}, {r::img_w, (float)Wo}, {r::score_thresh, (float)SCORE}};
             P.add(o);
         }
         const int N = DETS;
@@ -1711,16 +1637,14 @@ class RetinaNet : public ResNetFPN {
                              P.buf({B, K, N}, I32, "retina.kept.tb"), P.buf({B, K, N}, I32, "retina.kept.lbl"),
                              P.buf({B, K}, I32, "retina.kept.count")};
         {
+            namespace r = rec::retina_class_nms;
             OpRec o;
             o.kind = EDGEDET_OP_RETINA_CLASS_NMS;
             o.name = "retina.batched_nms";
-            const int64_t iv[5] = {B, L, KM, K, N};
-            for (int j = 0; j < 5; ++j) o.i[j] = iv[j];
-            for (int j = 0; j < 5; ++j) {
-                o.p[j] = P.ref(lrec[j]);
-                o.p[5 + j] = P.ref(crec[j]);
-            }
-            o.d[0] = NMS;
+            o.i = {{r::B, B}, {r::L, L}, {r::kin, KM}, {r::K, K}, {r::kmax, N}};
+            set_records(P, o, r::level0, lrec);
+            set_records(P, o, r::records0, crec);
+            o.d[r::iou] = NMS;
             P.add(o);
         }
         std::vector<float> ratio;
@@ -1733,20 +1657,8 @@ class RetinaNet : public ResNetFPN {
         P.out_score = P.buf({B, N}, 4, "out.scores");
         P.out_label = P.buf({B, N}, 8, "out.labels");
         P.out_count = P.buf({B}, I32, "out.count");
-        {
-            OpRec m;
-            m.kind = EDGEDET_OP_MERGE_TOPK;
-            m.name = "retina.detections_per_img";
-            const int64_t mv[4] = {B, K, N, N};
-            for (int j = 0; j < 4; ++j) m.i[j] = mv[j];
-            for (int j = 0; j < 5; ++j) m.p[j] = P.ref(crec[j]);
-            m.p[5] = P.ref(rbuf);
-            m.p[6] = P.ref(P.out_box);
-            m.p[7] = P.ref(P.out_score);
-            m.p[8] = P.ref(P.out_label);
-            m.p[9] = P.ref(P.out_count);
-            P.add(m);
-        }
+        merge_topk_op(P, "retina.detections_per_img", crec, P.ref(rbuf), P.ref(P.out_box), P.ref(P.out_score),
+                      P.ref(P.out_label), P.ref(P.out_count), B, K, N, N);
         P.input = bd.inp;
         P.dets = DETS;
         return Pp;

@@ -7,7 +7,8 @@ once into
     [K*K][C], SE fc weights transposed), uploaded once per model and shared by every plan of it;
   * one workspace (256-byte aligned carve-outs) holding every activation, the input staging buffer
     and the output buffers;
-  * an array of edgedet_op records (numpy, layout = include/edgedet.h) that libedgedet.so runs
+  * an array of edgedet_op records (numpy; struct = include/edgedet.h, the field layout of every
+    kind = csrc/records.hpp) that libedgedet.so runs
     directly or captures into a hipGraph replayed per batch.
 NativePlan is that plan on the Python side: the workspace as one torch allocation, the records
 resolved against it, and the named buffers.  Plan / conv_op below build records by hand for the
@@ -457,7 +458,8 @@ class NativePlan:
 def conv_op(plan, x, x_shape, w, bias, cout, k, stride, pad, act, y, y_shape, K, Kpad, res=None, res_hw=None,
             in_scale=None, y_pstride=None, y_bstride=None, y_off=0, x_pstride=None, x_bstride=None, tile=0,
             name="", in_shift=None, in_relu=False):
-    """Build a CONV record.  x_shape = (B, H, W, C) as laid out in x; y_shape = (B, Ho, Wo, Cout)."""
+    """Build a CONV record (the numbered slots are rec::conv of csrc/records.hpp, the layout's home).
+    x_shape = (B, H, W, C) as laid out in x; y_shape = (B, Ho, Wo, Cout)."""
     B, H, W, C = x_shape
     _, Ho, Wo, _ = y_shape
     assert Ho == (H + 2 * pad - k) // stride + 1 and Wo == (W + 2 * pad - k) // stride + 1, name

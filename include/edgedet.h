@@ -30,15 +30,15 @@ extern "C" {
 /*
  * One step of a static execution plan.  The Python host (edgeml_amd/plan.py) lowers a detector
  * into an array of these (BatchNorm folded, weights packed, buffers carved from one arena) and the
- * native executor launches them in order.  Field meaning per `kind` is documented in plan.py and
- * csrc/exec.cpp; sizes and pointers are plain integers so the layout is identical from ctypes.
+ * native executor launches them in order.  Field meaning per `kind` is documented in
+ * csrc/records.hpp; sizes and pointers are plain integers so the layout is identical from ctypes.
  */
 #define EDGEDET_OP_INTS 48
 #define EDGEDET_OP_PTRS 24
 #define EDGEDET_OP_DBLS 8
 #define EDGEDET_OP_FLTS 16
 
-/* One op record.  Field layouts per kind: csrc/exec.hip (header comment), e.g. DWCONV p0 x, p1 w,
+/* One op record.  Field layouts per kind: csrc/records.hpp (the named slots), e.g. DWCONV p0 x, p1 w,
  * p2 bias, p3 y, p4 SE partial sums; GROUP i0 = members. */
 typedef struct edgedet_op {
     int64_t kind;
