@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -227,69 +228,145 @@ __global__ void __launch_bounds__(256) dwconv_se_kernel(DwParams p) {
 // thread computes PW horizontally adjacent outputs of one channel quad, loading each input row
 // segment once into registers ((PW-1)*S+K f32x4 per kernel row instead of PW*K), so L1/TA traffic
 // per output drops by ~K/(1+(K-1)/PW).  Accumulation order per output is (kh, kw) as in the
-// scalar kernel.  SE variant: grid (cdiv(C/4,16), SE_PARTS, B), block = 16 quads x 16 group lanes,
-// partial sums per pixel-group split (see dwconv_se_kernel).
+// scalar kernel.
+// Load scheme: every input load is unconditional.  Row and column are clamped to a pixel of the
+// same image (dw_load_row) and a padded tap is zeroed after the load with a select (dw_fma_row), so
+// no load sits behind a branch and nothing waits for one row before the next is requested.
+// fmaf(+0, w, acc) returns acc for finite w, and acc is never -0 (it starts at +0 and exact
+// cancellation rounds to +0; only a product below 2^-150 could round to -0), so a zeroed tap leaves
+// what a skipped tap left.  dw_rows() kernel rows are in flight: a 3x3 thread issues all its loads
+// before the first use (one memory round trip); a 5x5 thread requests row kh + dw_rows() into the
+// slot of row kh as that is consumed (two round trips with three rows in flight; the stride-2 form,
+// whose row is 11 vectors, keeps two rows and makes three).  Addresses are a uniform base plus a
+// 32-bit byte offset per lane (the launcher sends an input of 2 GiB or more to the scalar kernels).
+// Flat and grouped form: the K weight vectors of a row travel with the row.  SE form: grid
+// (cdiv(C/4,16), SE_PARTS, B), block = 16 quads x 16 group lanes, partial sums per pixel-group
+// split (see dwconv_se_kernel); the K*K x 16-quad weight image is staged in LDS once per
+// workgroup, and the first rows of a lane's next group are requested before the current group's
+// activation and stores.
+template <int K, int S>
+constexpr int dw_rows() {
+    return K == 5 && S == 2 ? 2 : 3;
+}
+
+// Byte offsets of a group's (PW-1)*S+K input columns, clamped into the row, plus the lane's own.
 template <int K, int S, int PW>
-__device__ __forceinline__ void dw_group(const DwParams& p, const float* __restrict__ xb, int oh, int ow0, int c,
-                                         f32x4 (&acc)[PW]) {
-    constexpr int IW = (PW - 1) * S + K;
+__device__ __forceinline__ void dw_cols(const DwParams& p, uint32_t lane, int iw0, uint32_t (&co)[(PW - 1) * S + K]) {
+    const int cb = p.C * 4, hi = (p.W - 1) * cb;
+    int o = iw0 * cb;
 #pragma unroll
-    for (int o = 0; o < PW; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int ih0 = oh * S - p.pad, iw0 = ow0 * S - p.pad;
-#pragma unroll
-    for (int kh = 0; kh < K; ++kh) {
-        const int ih = ih0 + kh;
-        if ((unsigned)ih >= (unsigned)p.H) continue;
-        const float* row = xb + (int64_t)ih * p.W * p.C;
-        f32x4 xin[IW];
-#pragma unroll
-        for (int j = 0; j < IW; ++j) {
-            const int iw = iw0 + j;
-            xin[j] = (unsigned)iw < (unsigned)p.W ? *reinterpret_cast<const f32x4*>(row + (int64_t)iw * p.C)
-                                                  : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int kw = 0; kw < K; ++kw) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(p.w + (kh * K + kw) * p.C + c);
-#pragma unroll
-            for (int o = 0; o < PW; ++o) {
-                const f32x4 xv = xin[o * S + kw];
-                acc[o].x = fmaf(xv.x, wv.x, acc[o].x);
-                acc[o].y = fmaf(xv.y, wv.y, acc[o].y);
-                acc[o].z = fmaf(xv.z, wv.z, acc[o].z);
-                acc[o].w = fmaf(xv.w, wv.w, acc[o].w);
-            }
-        }
-    }
+    for (int j = 0; j < (PW - 1) * S + K; ++j, o += cb) co[j] = lane + (uint32_t)min(max(o, 0), hi);
 }
 
 template <int K, int S, int PW>
-__device__ __forceinline__ void dwconv_rb_body(const DwParams& p, int nq, int nwg, int64_t idx) {
-    const int64_t total = (int64_t)p.B * p.Ho * nwg * nq;
-    if (idx >= total) return;
-    const int q = (int)(idx % nq);
-    int64_t r = idx / nq;
-    const int wg = (int)(r % nwg);
-    r /= nwg;
-    const int oh = (int)(r % p.Ho);
-    const int b = (int)(r / p.Ho);
-    const int c = q * 4, ow0 = wg * PW;
-    f32x4 acc[PW];
-    dw_group<K, S, PW>(p, p.x + (int64_t)b * p.H * p.W * p.C + c, oh, ow0, c, acc);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + c);
-    float* yb = p.y + (((int64_t)b * p.Ho + oh) * p.Wo + ow0) * p.C + c;
-    const int act = p.act;
+__device__ __forceinline__ void dw_load_row(const DwParams& p, const float* __restrict__ base,
+                                            const uint32_t (&co)[(PW - 1) * S + K], int ih,
+                                            f32x4 (&x)[(PW - 1) * S + K]) {
+    const uint32_t ro = (uint32_t)(min(max(ih, 0), p.H - 1) * p.W) * (uint32_t)(p.C * 4);
+#pragma unroll
+    for (int j = 0; j < (PW - 1) * S + K; ++j)
+        x[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + (co[j] + ro));
+}
+
+// One kernel row into the PW accumulators; w(kw) is the row's kw-th weight vector.
+template <int K, int S, int PW, typename WF>
+__device__ __forceinline__ void dw_fma_row(const DwParams& p, int ih, int iw0, f32x4 (&x)[(PW - 1) * S + K], WF w,
+                                           f32x4 (&acc)[PW]) {
+    const bool rin = (unsigned)ih < (unsigned)p.H;
+#pragma unroll
+    for (int j = 0; j < (PW - 1) * S + K; ++j)
+        x[j] = rin && (unsigned)(iw0 + j) < (unsigned)p.W ? x[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 wv[K];
+#pragma unroll
+    for (int kw = 0; kw < K; ++kw) wv[kw] = w(kw);
+#pragma unroll
+    for (int kw = 0; kw < K; ++kw)
+#pragma unroll
+        for (int o = 0; o < PW; ++o) acc[o] = __builtin_elementwise_fma(x[o * S + kw], wv[kw], acc[o]);
+}
+
+// + bias, activation and the stores of one group; SUM: the SE squeeze sum, o = 0..PW-1 in order.
+template <int PW, bool SUM, typename AF>
+__device__ __forceinline__ void dw_store(const DwParams& p, float* yb, int ow0, const f32x4 (&acc)[PW],
+                                         const f32x4& bv, f32x4& sum, AF af) {
 #pragma unroll
     for (int o = 0; o < PW; ++o) {
         if (ow0 + o < p.Wo) {
             f32x4 v;
-            v.x = apply_act(acc[o].x + bv.x, act);
-            v.y = apply_act(acc[o].y + bv.y, act);
-            v.z = apply_act(acc[o].z + bv.z, act);
-            v.w = apply_act(acc[o].w + bv.w, act);
+            v.x = af(acc[o].x + bv.x);
+            v.y = af(acc[o].y + bv.y);
+            v.z = af(acc[o].z + bv.z);
+            v.w = af(acc[o].w + bv.w);
             *reinterpret_cast<f32x4*>(yb + (int64_t)o * p.C) = v;
+            if (SUM) sum += v;
         }
     }
+}
+
+// The activation is decided once per group, not per element (apply_act's expressions as they are).
+template <int PW, bool SUM>
+__device__ __forceinline__ void dw_finish(const DwParams& p, float* yb, int ow0, const f32x4 (&acc)[PW],
+                                          const f32x4& bv, f32x4& sum) {
+    const int act = p.act;
+    if (act == ACT_HSWISH)
+        dw_store<PW, SUM>(p, yb, ow0, acc, bv, sum, [](float v) { return apply_act(v, ACT_HSWISH); });
+    else if (act == ACT_RELU)
+        dw_store<PW, SUM>(p, yb, ow0, acc, bv, sum, [](float v) { return apply_act(v, ACT_RELU); });
+    else if (act == ACT_NONE)
+        dw_store<PW, SUM>(p, yb, ow0, acc, bv, sum, [](float v) { return apply_act(v, ACT_NONE); });
+    else
+        dw_store<PW, SUM>(p, yb, ow0, acc, bv, sum, [act](float v) { return apply_act(v, act); });
+}
+
+template <int K, int S, int PW>
+__device__ __forceinline__ void dwconv_rb_body(const DwParams& p, int nq, int nwg, int64_t idx) {
+    constexpr int IW = (PW - 1) * S + K;
+    const int64_t total = (int64_t)p.B * p.Ho * nwg * nq;
+    if (idx >= total) return;
+    int q, wg, oh, b;
+    if (total <= 0x7fffffff) {  // the usual case: 32-bit divisions before the first load
+        const uint32_t i = (uint32_t)idx, r0 = i / (uint32_t)nq, r1 = r0 / (uint32_t)nwg;
+        q = (int)(i - r0 * (uint32_t)nq);
+        wg = (int)(r0 - r1 * (uint32_t)nwg);
+        b = (int)(r1 / (uint32_t)p.Ho);
+        oh = (int)(r1 - (uint32_t)b * (uint32_t)p.Ho);
+    } else {
+        q = (int)(idx % nq);
+        int64_t r = idx / nq;
+        wg = (int)(r % nwg);
+        r /= nwg;
+        oh = (int)(r % p.Ho);
+        b = (int)(r / p.Ho);
+    }
+    constexpr int R = dw_rows<K, S>();
+    const int c = q * 4, ow0 = wg * PW;
+    const int ih0 = oh * S - p.pad, iw0 = ow0 * S - p.pad;
+    const float* wq = p.w + c;
+    uint32_t co[IW];
+    dw_cols<K, S, PW>(p, ((uint32_t)(b * p.H * p.W) * (uint32_t)p.C + (uint32_t)c) * 4u, iw0, co);
+    f32x4 buf[R][IW], wr[R][K], acc[PW];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        dw_load_row<K, S, PW>(p, p.x, co, ih0 + r, buf[r]);
+#pragma unroll
+        for (int kw = 0; kw < K; ++kw) wr[r][kw] = *reinterpret_cast<const f32x4*>(wq + (r * K + kw) * p.C);
+    }
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + c);
+#pragma unroll
+    for (int o = 0; o < PW; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kh = 0; kh < K; ++kh) {
+        const int sl = kh % R;
+        dw_fma_row<K, S, PW>(p, ih0 + kh, iw0, buf[sl], [&](int kw) { return wr[sl][kw]; }, acc);
+        if (kh + R < K) {
+            dw_load_row<K, S, PW>(p, p.x, co, ih0 + kh + R, buf[sl]);
+#pragma unroll
+            for (int kw = 0; kw < K; ++kw)
+                wr[sl][kw] = *reinterpret_cast<const f32x4*>(wq + ((kh + R) * K + kw) * p.C);
+        }
+    }
+    f32x4 unused;
+    dw_finish<PW, false>(p, p.y + (((int64_t)b * p.Ho + oh) * p.Wo + ow0) * p.C + c, ow0, acc, bv, unused);
 }
 
 template <int K, int S, int PW>
@@ -308,48 +385,97 @@ __global__ void __launch_bounds__(256) dwconv_rb_group_kernel(DwGroup g) {
     dwconv_rb_body<K, S, PW>(g.p[k], g.nq[k], g.nwg[k], (int64_t)(bx - g.start[k]) * blockDim.x + threadIdx.x);
 }
 
+// Compiled for three waves per SIMD (168 VGPRs), which holds the rows in flight without scratch; the
+// 3x3 stride-2 form (27 vectors in flight) needs the room of two.
+template <int K, int S>
+constexpr int dw_se_waves() {
+    return K == 3 && S == 2 ? 2 : 3;
+}
+
 template <int K, int S, int PW, int QL = 16>
-__global__ void __launch_bounds__(256) dwconv_rb_se_kernel(DwParams p, int nq, int nwg) {
+__global__ void __launch_bounds__(256, (dw_se_waves<K, S>())) dwconv_rb_se_kernel(DwParams p, int nq, int nwg) {
     constexpr int GL = 256 / QL;  // group lanes per channel quad (QL quads per workgroup)
+    constexpr int IW = (PW - 1) * S + K, R = dw_rows<K, S>();
     __shared__ f32x4 red[GL][QL];
+    constexpr int WU = ((K * K + 1) * QL + 255) / 256;
+    // the workgroup's weights by tap and channel quad; row K * K: the bias; the rest pads to WU rows per lane
+    __shared__ f32x4 wl[WU * GL][QL];
     const int ql = threadIdx.x % QL, gl = threadIdx.x / QL;
     const int q = blockIdx.x * QL + ql;
     const int c = q * 4;
     const int sidx = blockIdx.y, b = blockIdx.z;
     const int G = p.Ho * nwg;
     const int g0 = (int)((int64_t)sidx * G / p.parts), g1 = (int)((int64_t)(sidx + 1) * G / p.parts);
+    const bool live = q < nq;
+    const int cl = live ? c : (nq - 1) * 4;  // a lane past the last quad loads the last quad's, and stores nothing
+    const float* xb = p.x + (int64_t)b * p.H * p.W * p.C;
     f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    if (q < nq) {
-        const float* xb = p.x + (int64_t)b * p.H * p.W * p.C + c;
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + c);
-        const int act = p.act;
-        for (int g = g0 + gl; g < g1; g += GL) {
-            const int oh = g / nwg, ow0 = (g - oh * nwg) * PW;
-            f32x4 acc[PW];
-            dw_group<K, S, PW>(p, xb, oh, ow0, c, acc);
-            float* yb = p.y + (((int64_t)b * p.Ho + oh) * p.Wo + ow0) * p.C + c;
+    f32x4 buf[R][IW];
+    int g = g0 + gl;
+    if (live && g < g1) {
+        const int oh = g / nwg, ow0 = (g - oh * nwg) * PW;
+        uint32_t co[IW];
+        dw_cols<K, S, PW>(p, (uint32_t)cl * 4u, ow0 * S - p.pad, co);
 #pragma unroll
-            for (int o = 0; o < PW; ++o) {
-                if (ow0 + o < p.Wo) {
-                    f32x4 v;
-                    v.x = apply_act(acc[o].x + bv.x, act);
-                    v.y = apply_act(acc[o].y + bv.y, act);
-                    v.z = apply_act(acc[o].z + bv.z, act);
-                    v.w = apply_act(acc[o].w + bv.w, act);
-                    *reinterpret_cast<f32x4*>(yb + (int64_t)o * p.C) = v;
-                    sum += v;
-                }
+        for (int r = 0; r < R; ++r) dw_load_row<K, S, PW>(p, xb, co, oh * S - p.pad + r, buf[r]);
+    }
+    {  // WU vectors per thread (rows past K * K read the bias again): loads and LDS stores are
+       // unconditional, so the loads go out together with the first group's rows
+        f32x4 wv[WU];
+        const int tq = min(q, nq - 1) * 4;
+#pragma unroll
+        for (int u = 0; u < WU; ++u) {
+            const int t = gl + u * GL;
+            wv[u] = *reinterpret_cast<const f32x4*>((t < K * K ? p.w + t * p.C : p.bias) + tq);
+        }
+#pragma unroll
+        for (int u = 0; u < WU; ++u) wl[gl + u * GL][ql] = wv[u];
+    }
+    __syncthreads();
+    // One group.  Row kh sits in slot kh % R, and the slot a row leaves takes row kh + R of this group
+    // or, past the last row, the row of the lane's next group that belongs there (MORE).  The last
+    // group is a second copy of the body: a branch around the refill inside the loop makes hipcc
+    // keep both the old and the new rows in registers.
+    auto pass = [&](auto more) {
+        constexpr bool MORE = decltype(more)::value;
+        const int oh = g / nwg, ow0 = (g - oh * nwg) * PW;
+        const int ih0 = oh * S - p.pad, iw0 = ow0 * S - p.pad;
+        const int gn = g + GL;
+        const int ohn = gn / nwg, ih0n = ohn * S - p.pad, iw0n = (gn - ohn * nwg) * PW * S - p.pad;
+        int qv = ql;  // opaque per pass: the LDS weight reads stay in the loop, next to their use
+        asm volatile("" : "+v"(qv));
+        f32x4 acc[PW];
+#pragma unroll
+        for (int o = 0; o < PW; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kh = 0; kh < K; ++kh) {
+            const int sl = kh % R;
+            dw_fma_row<K, S, PW>(p, ih0 + kh, iw0, buf[sl], [&](int kw) { return wl[kh * K + kw][qv]; }, acc);
+            if (kh + R < K || MORE) {
+                const bool own = kh + R < K;
+                uint32_t co[IW];
+                dw_cols<K, S, PW>(p, (uint32_t)cl * 4u, own ? iw0 : iw0n, co);
+                dw_load_row<K, S, PW>(p, xb, co, own ? ih0 + kh + R : ih0n + sl, buf[sl]);
             }
         }
+        dw_finish<PW, true>(p, p.y + (((int64_t)b * p.Ho + oh) * p.Wo + ow0) * p.C + c, ow0, acc, wl[K * K][qv], sum);
+        g = gn;
+    };
+    if (live && g < g1) {
+        while (g + GL < g1) pass(std::true_type{});
+        pass(std::false_type{});
     }
     red[gl][ql] = sum;
     __syncthreads();
-    if (gl == 0 && q < nq) {
+    if (gl == 0 && live) {
         f32x4 t = red[0][ql];
         for (int k = 1; k < GL; ++k) t += red[k][ql];
         *reinterpret_cast<f32x4*>(p.part + ((int64_t)b * p.parts + sidx) * p.C + c) = t;
     }
 }
+
+// The register-blocked kernels address the input by 32-bit byte offsets.
+static bool dw_offsets_fit(const DwParams& p) { return (int64_t)p.B * p.H * p.W * p.C * 4 < (1ll << 31); }
 
 template <int K, int S>
 static int dwconv_rb_launch(const DwParams& p, hipStream_t s) {
@@ -378,7 +504,7 @@ static int dwconv_rb_launch(const DwParams& p, hipStream_t s) {
 //   2. stem outputs on the 18 x 18 halo (zero outside the map: the depthwise pads them) as a GEMM on
 //      the matrix cores, [324 halo pixels] x [36 = 9 taps x 4 channels] x [16], one
 //      v_mfma_f32_16x16x4_f32 per tap (exact fp32 products);
-//   3. per output pixel: depthwise on the vector ALUs (taps (kh, kw) as dw_group), then the projection
+//   3. per output pixel: depthwise on the vector ALUs (taps (kh, kw) as dw_fma_row), then the projection
 //      as a [256 pixels] x [16] x [16] MFMA GEMM, + bias, + residual.
 // The matrix-core form replaced one pixel x 16 channels per thread on the vector ALUs for phases 2 and
 // 3 (SSD 30.63k / 30.63k -> 30.87k / 30.95k img/s in ABBA-ordered runs, profiles/r4c_ab.txt).  The
@@ -877,7 +1003,8 @@ int dwconv_group_launch(const DwParams* ps, int n, hipStream_t s) {
     for (int k = 0; k < n; ++k) {
         const DwParams& p = ps[k];
         EDGEDET_REQUIRE(p.x && p.w && p.bias && p.y && p.C % 4 == 0, "dwconv group: null pointer or C % 4 != 0");
-        if (p.K != K || p.stride != S || p.part || !((K == 3 || K == 5) && (S == 1 || S == 2))) return 1;
+        if (p.K != K || p.stride != S || p.part || !((K == 3 || K == 5) && (S == 1 || S == 2)) || !dw_offsets_fit(p))
+            return 1;
         g.p[k] = p;
         g.nq[k] = p.C / 4;
         g.nwg[k] = cdiv(p.Wo, PW);
@@ -897,10 +1024,12 @@ int dwconv_launch(const DwParams& p, hipStream_t s) {
     EDGEDET_REQUIRE(p.x && p.w && p.bias && p.y, "dwconv: null x/w/bias/y");
     EDGEDET_REQUIRE(p.C % 4 == 0, "dwconv: C must be a multiple of 4");
     if (p.part) EDGEDET_REQUIRE(p.parts >= 1 && p.parts <= SE_PARTS, "dwconv: 1..16 SE partial sums");
-    if (p.K == 3 && p.stride == 1) return dwconv_rb_launch<3, 1>(p, s);
-    if (p.K == 3 && p.stride == 2) return dwconv_rb_launch<3, 2>(p, s);
-    if (p.K == 5 && p.stride == 1) return dwconv_rb_launch<5, 1>(p, s);
-    if (p.K == 5 && p.stride == 2) return dwconv_rb_launch<5, 2>(p, s);
+    if (dw_offsets_fit(p)) {
+        if (p.K == 3 && p.stride == 1) return dwconv_rb_launch<3, 1>(p, s);
+        if (p.K == 3 && p.stride == 2) return dwconv_rb_launch<3, 2>(p, s);
+        if (p.K == 5 && p.stride == 1) return dwconv_rb_launch<5, 1>(p, s);
+        if (p.K == 5 && p.stride == 2) return dwconv_rb_launch<5, 2>(p, s);
+    }
     if (p.part) {
         hipLaunchKernelGGL(dwconv_se_kernel, dim3((unsigned)cdiv(p.C, 64), p.parts, p.B), dim3(256), 0, s, p);
         EDGEDET_LAUNCH_CHECK();
