@@ -43,7 +43,7 @@ def _deps():
 
 
 def write_tile_table(objdir):
-    """The tuned conv tile table (data/conv_tiles_gfx950.json, also read by plan.py) as a C++
+    """The tuned conv tile table (data/conv_tiles_gfx950.json, written by tools/tune_conv.py) as a C++
     initializer list for the native lowering (csrc/lower.hip)."""
     import json
     with open(TILES_JSON) as f:

@@ -2,12 +2,12 @@
 //
 // The reference's seam is the torchvision model call model(images) -> boxes/scores/labels
 // (detect.py:72,78).  This file turns a detector configuration (SSDLite320-MobileNetV3 of
-// detect.py:24/26, Faster R-CNN R50-FPN-v2 of detect.py:30/32) into the same static execution plan
-// the Python host builds (edgeml_amd/models.py + plan.py): packed weights (BatchNorm folded in
-// float64, conv weights K-contiguous with K padded to 32, bf16x3 planes, depthwise tap-major, SE fc2
-// transposed, FC6 permuted to (h, w, c), predictor rows [bbox | cls]), one workspace carved into
-// buffers in the same order with the same 256-byte alignment, and the same op records (tiles from
-// the same tuned table).  So a C / C++ / Go host can run a detector with nothing but this library:
+// detect.py:24/26, Faster R-CNN R50-FPN-v2 of detect.py:30/32) into a static execution plan, the
+// only lowering there is (the Python model objects of edgeml_amd/models.py run its plans): packed
+// weights (BatchNorm folded in float64, conv weights K-contiguous with K padded to 32, bf16x3 planes,
+// depthwise tap-major, SE fc2 transposed, FC6 permuted to (h, w, c), predictor rows [bbox | cls]),
+// one workspace carved into 256-byte aligned buffers, and the op records (tiles from the tuned
+// table).  So a C / C++ / Go host can run a detector with nothing but this library:
 //   edgedet_<model>_pack            torchvision-named host tensors -> packed weight blob (host)
 //   edgedet_<model>_workspace_size  bytes of the caller-owned workspace for (B, H, W, input dtype)
 //   edgedet_<model>_prepare         write the plan's constants (anchors, rescale ratios) into it
@@ -41,14 +41,44 @@ static const std::unordered_map<std::string, int>& tile_table() {
     return t;
 }
 
-static bool env_is(const char* k, const char* v, const char* dflt) {
-    const char* e = getenv(k);
-    return std::string(e ? e : dflt) == v;
-}
-static int env_int(const char* k, int dflt) {
-    const char* e = getenv(k);
-    return e && *e ? atoi(e) : dflt;
-}
+// ------------------------------------------------------------------------------------ options
+// Every switch of the lowering.  A plan is lowered under one Options value, stores it, and is cached
+// under it (plan_for), so flipping a switch never returns a plan lowered under the old setting.  The
+// values are normalised: settings that lower identically compare equal and share one plan.
+struct Options {
+    bool bf16x6 = true;     // EDGEDET_CONV_MATH: conv math of the compute-bound tiles; off only for "f32"
+    bool tuned = true;      // EDGEDET_CONV_TUNED: tiles from the tuned table (unset, empty or 1)
+    int ssd_chains = 2;     // EDGEDET_SSD_CHAINS: most batch chains of an SSDLite plan (0 or unset: 2)
+    bool stem_fuse = true;  // EDGEDET_SSD_STEM_FUSE: transform + stem + block 0.1 as one record (unset or 1)
+    bool mb_block = true;   // EDGEDET_MB_BLOCK: blocks 0.2 / 0.3 as one MBCONV record each (unset or 1)
+    bool rpn_split = true;  // EDGEDET_RPN_SPLIT: RPN NMS split over many workgroups (unless it parses to 0)
+    // Redzone (diagnostic, edgedet_set_redzone; 0 in production): bytes left unused before the first
+    // workspace buffer, between consecutive buffers and after the last, so a test can fill them with a
+    // canary and find any kernel that writes outside its buffers.
+    int64_t redzone = 0;
+
+    auto tie() const { return std::tie(bf16x6, tuned, ssd_chains, stem_fuse, mb_block, rpn_split, redzone); }
+    bool operator<(const Options& o) const { return tie() < o.tie(); }
+
+    // The process environment, read at every plan lookup: the only getenv calls of the lowering.
+    static Options from_env(int64_t redzone) {
+        auto num = [](const char* k, int dflt) {  // unset or empty: the default
+            const char* e = getenv(k);
+            return e && *e ? atoi(e) : dflt;
+        };
+        Options o;
+        const char* math = getenv("EDGEDET_CONV_MATH");
+        o.bf16x6 = !(math && std::string(math) == "f32");
+        o.tuned = num("EDGEDET_CONV_TUNED", 1) == 1;
+        const int chains = num("EDGEDET_SSD_CHAINS", 0);
+        o.ssd_chains = std::max(1, std::min(chains ? chains : 2, EDGEDET_MAX_LANES));
+        o.stem_fuse = num("EDGEDET_SSD_STEM_FUSE", 1) == 1;
+        o.mb_block = num("EDGEDET_MB_BLOCK", 1) == 1;
+        o.rpn_split = num("EDGEDET_RPN_SPLIT", 1) != 0;
+        o.redzone = redzone;
+        return o;
+    }
+};
 
 enum Act { A_NONE = 0, A_RE = 1, A_R6 = 2, A_HS = 3 };
 
@@ -74,7 +104,7 @@ struct WRef {
     int64_t split = -1;       // float offset of the bf16x3 planes (conv weights)
 };
 
-// plan.py WeightPack: arrays at 64-float boundaries.
+// The weight blob: arrays at 64-float boundaries.
 struct Pack {
     bool values = false;
     std::vector<float> blob;
@@ -107,7 +137,7 @@ static uint16_t bf16_rn(float x, float* back) {
     return (uint16_t)r;
 }
 
-// plan.split_bf16x3: x0 = RN(x), x1 = RN(x - x0), x2 = RN(x - x0 - x1); planes [3][n] of rows of
+// x0 = RN(x), x1 = RN(x - x0), x2 = RN(x - x0 - x1); planes [3][n] of rows of
 // kpad, x = -w in the odd 32-wide K blocks (the bf16x6 kernels' sign-alternated stages).
 static std::vector<uint16_t> split_bf16x3(const std::vector<float>& w, int64_t kpad) {
     const size_t n = w.size();
@@ -306,12 +336,9 @@ struct External {
     }
 };
 
-// Redzone (diagnostic, edgedet_set_redzone; 0 in production): bytes left unused before the first
-// workspace buffer, between consecutive buffers and after the last, so a test can fill them with a
-// canary and find any kernel that writes outside its buffers.
-static int64_t g_redzone = 0;
-
 struct Plan {
+    explicit Plan(const Options& o) : opt(o) {}
+    const Options opt;  // what this plan was lowered under
     std::shared_ptr<const std::vector<edgedet_op>> resolved;  // records of the last forward's pointers
     External resolved_for;
     std::vector<Buf> bufs;
@@ -356,7 +383,7 @@ struct Plan {
         r.byte_off = byte_off;
         return r;
     }
-    // BufView: images [b0, b0 + n) of a batch-leading buffer
+    // images [b0, ...) of a batch-leading buffer
     Ref view(int b, int64_t b0) const { return ref(b, b0 * (bufs[(size_t)b].nbytes / bufs[(size_t)b].shape[0])); }
     static Ref wref(const WRef& w) {
         Ref r;
@@ -408,7 +435,7 @@ struct Plan {
         forked = 0;
     }
     void finalize() {
-        const int64_t rz = g_redzone;
+        const int64_t rz = opt.redzone;
         int64_t off = rz;
         for (auto& b : bufs) {
             b.off = off;
@@ -448,7 +475,8 @@ struct ConvArgs {
     std::string name;
 };
 
-// plan.conv_op
+// One CONV record (rec::conv), its tile from the tuned table, with the MEMSET a split-K tile needs
+// in front of it and the pre-split scratch an input transform gets.
 static void conv_op(Plan& P, const ConvArgs& a) {
     const int64_t B = a.xs[0], H = a.xs[1], W = a.xs[2], C = a.xs[3];
     const int64_t Ho = a.ys[1], Wo = a.ys[2];
@@ -459,7 +487,6 @@ static void conv_op(Plan& P, const ConvArgs& a) {
     const int64_t yp = a.y_pstride < 0 ? a.cout : a.y_pstride;
     const int64_t rH = a.res_h < 0 ? Ho : a.res_h, rW = a.res_w < 0 ? Wo : a.res_w;
     namespace r = rec::conv;
-    const bool bf16x6 = !env_is("EDGEDET_CONV_MATH", "f32", "bf16x6");
     OpRec o;
     o.kind = EDGEDET_OP_CONV;
     o.name = a.name;
@@ -470,10 +497,10 @@ static void conv_op(Plan& P, const ConvArgs& a) {
            {r::y_bstride, a.y_bstride < 0 ? Ho * Wo * yp : a.y_bstride}, {r::res_bstride, rH * rW * a.cout},
            {r::y_off, a.y_off}, {r::res_H, rH}, {r::res_W, rW}, {r::tile, a.tile}, {r::in_relu, a.in_relu ? 1 : 0}};
     o.p = {{r::x, a.x}, {r::w, Plan::wref(a.w.w)}, {r::bias, Plan::wref(a.w.b)}, {r::y, a.y}, {r::res, a.res},
-           {r::in_scale, a.in_scale}, {r::w3, bf16x6 ? Plan::wsplit(a.w.w) : Ref()}, {r::in_shift, a.in_shift}};
+           {r::in_scale, a.in_scale}, {r::w3, P.opt.bf16x6 ? Plan::wsplit(a.w.w) : Ref()}, {r::in_shift, a.in_shift}};
     const bool w3 = o.p[r::w3].kind != Ref::NONE;
     int64_t& tile = o.i[r::tile];
-    if (!a.tile && env_int("EDGEDET_CONV_TUNED", 1) == 1) {
+    if (!a.tile && P.opt.tuned) {
         auto it = tile_table().find(conv_key(o));
         if (it != tile_table().end() && it->second && (w3 || it->second < 20)) tile = it->second;
     }
@@ -652,12 +679,12 @@ class SSDLite {
 
     SSDLite(const Config& c, Packer& pk) : cfg_(c), pk_(pk), blocks_(mnv3_blocks(c.reduced_tail)) {}
 
-    // models.SSDLite320._pack_all: build_plan(1, 320, 320, pack_only=True) walks the network in order
-    void pack_all() { lower(1, S, S, false, true); }
+    // the weight blob's layout: one pack-only walk of the network in order, on default options
+    void pack_all() { lower(1, S, S, false, Options(), true); }
 
-    std::unique_ptr<Plan> lower(int B, int H, int W, bool u8, bool pack_only = false) {
-        auto P = std::make_unique<Plan>();
-        int nch = pack_only ? 1 : n_chains(B);
+    std::unique_ptr<Plan> lower(int B, int H, int W, bool u8, const Options& opt, bool pack_only = false) {
+        auto P = std::make_unique<Plan>(opt);
+        int nch = pack_only ? 1 : n_chains(B, opt);
         const int inp = P->buf({B, 3, H, W}, u8 ? 1 : 4, "images");
         Shared sh;
         if (nch > 1) P->fork(nch - 1);
@@ -684,10 +711,8 @@ class SSDLite {
             oc = -1;
     };
 
-    int n_chains(int B) const {
-        const int n = env_int("EDGEDET_SSD_CHAINS", 0) ? env_int("EDGEDET_SSD_CHAINS", 0) : 2;
-        return std::max(1, std::min({n, EDGEDET_MAX_LANES, B >= 16 ? B / 8 : 1}));
-    }
+    // at least eight images per chain, and none below a batch of 16
+    static int n_chains(int B, const Options& opt) { return std::min(opt.ssd_chains, B >= 16 ? B / 8 : 1); }
 
     ConvW cbn(const std::string& prefix, int64_t cout, int64_t cin, int k, bool dw, int64_t cin_pad = 0) {
         return pk_.conv_bn(prefix + ".0.weight", prefix + ".1", EPS, cout, cin, k, dw, cin_pad);
@@ -700,7 +725,7 @@ class SSDLite {
         auto view = [&](int b) { return nch > 1 ? P.view(b, img0) : P.ref(b); };
         // the transform (normalise 0.5 / 0.5, resize to S x S): folded into the fused stem's input loads
         // (EDGEDET_SSD_STEM_FUSE=1, the default), else its own record into an NHWC4 buffer
-        const bool stem_fuse = env_int("EDGEDET_SSD_STEM_FUSE", 1) == 1 && !pack_only;
+        const bool stem_fuse = P.opt.stem_fuse && !pack_only;
         Cur cur;
         if (!stem_fuse) {
             const int x = P.buf({B, S, S, 4}, 4, "pre" + sfx);
@@ -799,7 +824,7 @@ class SSDLite {
             Prefixes pf = block_prefixes(b, base);
             // blocks 0.2 / 0.3 as one MBCONV launch each (EDGEDET_MB_BLOCK=0: the three separate ops);
             // SSD 27.5k -> 28.4k img/s with the 8-wave kernel (r3g); one wave per 16 channels since r3n
-            if (env_int("EDGEDET_MB_BLOCK", 1) == 1 && !pack_only && !pf.pe.empty() && !b.se && b.cin <= 32 &&
+            if (P.opt.mb_block && !pack_only && !pf.pe.empty() && !b.se && b.cin <= 32 &&
                 b.cin % 4 == 0 && b.cout <= 32 && b.exp <= 128)
                 return mb_block(in, b, pf);
             Cur y = in;
@@ -913,7 +938,7 @@ class SSDLite {
             a.y_pstride = 6 * h.cols;
             a.y_bstride = A * h.cols;
             a.y_off = (int64_t)img0 * A * h.cols + h.off * h.cols;
-            a.tile = env_is("EDGEDET_CONV_MATH", "f32", "bf16x6") ? 0 : HEAD_TILE;  // f32: alone
+            a.tile = P.opt.bf16x6 ? HEAD_TILE : 0;  // f32: alone
             a.name = h.p + ".1" + sfx;
             conv_op(P, a);
         }
@@ -1017,7 +1042,7 @@ class SSDLite {
 };
 
 // ------------------------------------------------------------------------------------ Faster R-CNN
-// Shared by Faster R-CNN and RetinaNet (models.FasterRCNNFPNv2._lower_body): GeneralizedRCNNTransform
+// Shared by Faster R-CNN and RetinaNet: GeneralizedRCNNTransform
 // (min 800 / max 1333, ImageNet mean / std, pad to /32) and the ResNet-50 body C2..C5.
 class ResNetFPN {
   public:
@@ -1039,7 +1064,7 @@ class ResNetFPN {
     }
 
   protected:
-    // options of one conv (models.FasterRCNNFPNv2._lower_body.conv): BatchNorm prefix, or a bias key,
+    // options of one conv: BatchNorm prefix, or a bias key,
     // or neither (no bias: RetinaNet GroupNorm towers); fused input transform; strided output
     struct COpt {
         std::string bnp, bias_key, name;
@@ -1217,10 +1242,10 @@ class FasterRCNN : public ResNetFPN {
 
     FasterRCNN(const Config& c, Packer& pk) : ResNetFPN(c, pk) {}
 
-    void pack_all() { lower(1, MIN_SIZE, MIN_SIZE, false, true); }
+    void pack_all() { lower(1, MIN_SIZE, MIN_SIZE, false, Options(), true); }
 
-    std::unique_ptr<Plan> lower(int B, int H, int W, bool u8, bool pack_only = false) {
-        auto Pp = std::make_unique<Plan>();
+    std::unique_ptr<Plan> lower(int B, int H, int W, bool u8, const Options& opt, bool pack_only = false) {
+        auto Pp = std::make_unique<Plan>(opt);
         Plan& P = *Pp;
         const int NC = cfg_.num_classes;
         Body bd = body(P, B, H, W, u8);
@@ -1262,7 +1287,7 @@ class FasterRCNN : public ResNetFPN {
         // the big level's tail instead of running as eight latency-bound launches after it (round 3 ran
         // the levels one after another on the caller stream; on four stream lanes was 0.75 % slower).
         const int L5 = (int)outs.size();
-        const bool grouped = !env_is("EDGEDET_CONV_MATH", "f32", "bf16x6");  // grouped launches: bf16x6 tiles
+        const bool grouped = P.opt.bf16x6;  // grouped launches: bf16x6 tiles
         std::vector<Cur> t0s, t1s;
         if (grouped) group_op(P, "rpn.head.conv.0", L5);
         for (int lvl = 0; lvl < L5; ++lvl) {
@@ -1327,7 +1352,7 @@ class FasterRCNN : public ResNetFPN {
             o.i[r::nchunk] = nch;
             // split NMS (selection / IoU mask over many workgroups / scan): EDGEDET_RPN_SPLIT=0 keeps one
             // workgroup per (level, image) for the whole segment
-            if (env_int("EDGEDET_RPN_SPLIT", 1))
+            if (P.opt.rpn_split)
                 o.p[r::split] = P.ref(P.buf({rpn_split_bytes((int64_t)B * L)}, 1, "rpn.nms.split"));
             P.add(o);
         }
@@ -1495,10 +1520,10 @@ class RetinaNet : public ResNetFPN {
 
     RetinaNet(const Config& c, Packer& pk) : ResNetFPN(c, pk) {}
 
-    void pack_all() { lower(1, MIN_SIZE, MIN_SIZE, false, true); }
+    void pack_all() { lower(1, MIN_SIZE, MIN_SIZE, false, Options(), true); }
 
-    std::unique_ptr<Plan> lower(int B, int H, int W, bool u8, bool pack_only = false) {
-        auto Pp = std::make_unique<Plan>();
+    std::unique_ptr<Plan> lower(int B, int H, int W, bool u8, const Options& opt, bool pack_only = false) {
+        auto Pp = std::make_unique<Plan>(opt);
         Plan& P = *Pp;
         const int K = cfg_.num_classes;
         Body bd = body(P, B, H, W, u8);
@@ -1687,7 +1712,8 @@ struct Engine {
     std::unique_ptr<SSDLite> ssd;
     std::unique_ptr<FasterRCNN> frcnn;
     std::unique_ptr<RetinaNet> retina;
-    std::map<std::tuple<int, int, int, bool, int64_t>, std::unique_ptr<Plan>> plans;  // (B, H, W, u8, redzone)
+    using Shape = std::tuple<int, int, int, bool>;  // (B, H, W, u8)
+    std::map<std::pair<Shape, Options>, std::unique_ptr<Plan>> plans;
     uint64_t clock = 0;
 };
 constexpr size_t PLAN_CACHE = 64;
@@ -1712,6 +1738,7 @@ static std::unique_ptr<Engine> make_engine(const Config& c, const Params* values
 }
 
 static std::mutex g_mu;
+static int64_t g_redzone = 0;  // edgedet_set_redzone: Options::redzone of every later plan lookup
 static std::map<std::tuple<int, int, int>, std::unique_ptr<Engine>> g_engines;
 
 static Engine* engine(const Config& c) {
@@ -1722,7 +1749,9 @@ static Engine* engine(const Config& c) {
 }
 
 static Plan* plan_for(Engine* e, int B, int H, int W, bool u8) {
-    auto key = std::make_tuple(B, H, W, u8, g_redzone);  // a redzone layout never serves a plain lowering
+    // the switches and the redzone are part of the key: a plan lowered under one setting never serves another
+    const Options opt = Options::from_env(g_redzone);
+    auto key = std::make_pair(Engine::Shape(B, H, W, u8), opt);
     auto it = e->plans.find(key);
     if (it != e->plans.end()) {
         it->second->last_use = ++e->clock;
@@ -1734,9 +1763,9 @@ static Plan* plan_for(Engine* e, int B, int H, int W, bool u8) {
             if (i->second->last_use < lru->second->last_use) lru = i;
         e->plans.erase(lru);
     }
-    std::unique_ptr<Plan> p = e->cfg.kind == 0   ? e->ssd->lower(B, H, W, u8)
-                              : e->cfg.kind == 1 ? e->frcnn->lower(B, H, W, u8)
-                                                 : e->retina->lower(B, H, W, u8);
+    std::unique_ptr<Plan> p = e->cfg.kind == 0   ? e->ssd->lower(B, H, W, u8, opt)
+                              : e->cfg.kind == 1 ? e->frcnn->lower(B, H, W, u8, opt)
+                                                 : e->retina->lower(B, H, W, u8, opt);
     p->finalize();
     p->last_use = ++e->clock;
     Plan* raw = p.get();
@@ -1809,7 +1838,7 @@ static int shape_ok(int32_t B, int32_t H, int32_t W) {
 extern "C" int edgedet_set_redzone(int64_t bytes) {
     EDGEDET_REQUIRE(bytes >= 0 && bytes % 256 == 0 && bytes <= (64 << 20), "set_redzone: 0..64 MiB, multiple of 256");
     std::lock_guard<std::mutex> g(g_mu);
-    g_redzone = bytes;  // part of the plan cache key: every later lookup lowers (or finds) the new layout
+    g_redzone = bytes;  // part of the plan cache key (Options): every later lookup lowers (or finds) the new layout
     return 0;
 }
 
@@ -1980,7 +2009,9 @@ extern "C" int edgedet_model_release(int32_t kind, int32_t num_classes, int32_t 
     if (config_of(kind, num_classes, reduced_tail, &c) || shape_ok(B, H, W)) return -1;
     EDGEDET_TRY({
         std::lock_guard<std::mutex> g(g_mu);
-        engine(c)->plans.erase(std::make_tuple(B, H, W, input_u8 != 0, g_redzone));
+        auto& plans = engine(c)->plans;  // every lowering of the shape, whatever its options
+        const Engine::Shape shape(B, H, W, input_u8 != 0);
+        for (auto it = plans.begin(); it != plans.end();) it = it->first.first == shape ? plans.erase(it) : std::next(it);
         return 0;
     })
 }

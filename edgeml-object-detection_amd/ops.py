@@ -28,6 +28,7 @@ WAIT = 23
 GROUP = 25  # the next i[0] records (CONV or DWCONV) issued as one grouped launch
 MAX_GROUP = 12
 LANE_FIELD, MAX_LANES = 47, 4
+CONV_TILE = 23  # the tile slot of a CONV record (rec::conv::tile, csrc/records.hpp)
 
 SE_PARTS = 16  # max pixel splits of the SE squeeze partial sums (csrc/kernels.hpp SE_PARTS)
 
@@ -275,6 +276,35 @@ def split_bf16x3(w):
     return out
 
 
+def conv_record(x_shape, cout, k, stride, pad, act, x, w, bias, y, res=None, in_scale=None, w3=None, in_shift=None,
+                x3=None, x_pstride=None, y_pstride=None, res_pstride=None, x_bstride=None, y_bstride=None,
+                res_bstride=None, y_off=0, res_hw=None, tile=0, in_relu=False):
+    """A one-element CONV record array.  x_shape = (B, H, W, Cin); the pointers are device tensors,
+    addresses or None; strides are in elements and default to the dense layout, res_hw (the residual's
+    size, nearest-upsampled to the output) to the output's.  The slots below are rec::conv of
+    csrc/records.hpp, the layout's home, in its order."""
+    B, H, W, Cin = x_shape
+    Ho = (H + 2 * pad - k) // stride + 1
+    Wo = (W + 2 * pad - k) // stride + 1
+    xp = Cin if x_pstride is None else x_pstride
+    yp = cout if y_pstride is None else y_pstride
+    rp = cout if res_pstride is None else res_pstride
+    rH, rW = (Ho, Wo) if res_hw is None else res_hw
+    rec = np.zeros(1, dtype=OP_DTYPE)
+    rec[0]["kind"] = CONV
+    ints = [B, H, W, Cin, Ho, Wo, cout, k, k, stride, pad, ACT[act],              # B .. act
+            k * k * Cin, int(lib().edgedet_conv_weight_k(k, k, Cin)),              # K, Kpad
+            xp, yp, rp,                                                            # x / y / res_pstride
+            H * W * xp if x_bstride is None else x_bstride,                        # x_bstride
+            Ho * Wo * yp if y_bstride is None else y_bstride,                      # y_bstride
+            rH * rW * rp if res_bstride is None else res_bstride,                  # res_bstride
+            y_off, rH, rW, tile, int(in_relu)]                                     # y_off, res_H, res_W, tile, in_relu
+    rec[0]["i"][:len(ints)] = ints
+    for j, t in enumerate((x, w, bias, y, res, in_scale, w3, in_shift, x3)):      # x .. x3
+        rec[0]["p"][j] = 0 if t is None else t.data_ptr() if torch.is_tensor(t) else int(t)
+    return rec
+
+
 def conv2d_nhwc(x, w_packed, bias, cout, k, stride, pad, act=None, res=None, tile=0, in_scale=None, w3=None,
                 presplit=False):
     """Fused conv (+ folded BN) + residual + activation on NHWC; w_packed from plan.pack_conv_weight.
@@ -302,15 +332,8 @@ def conv2d_nhwc(x, w_packed, bias, cout, k, stride, pad, act=None, res=None, til
             check(lib().edgedet_conv2d_ex(_ptr(x), B, H, W, Cin, _ptr(w_packed), _ptr(w3), _ptr(bias), cout, k, k,
                                           stride, pad, ACT[act], _ptr(res), _ptr(y), 0, stream_handle()))
         return y
-    K = k * k * Cin
-    kpad = int(lib().edgedet_conv_weight_k(k, k, Cin))
-    rec = np.zeros(1, dtype=OP_DTYPE)
-    rec[0]["kind"] = CONV
-    vals = [B, H, W, Cin, Ho, Wo, cout, k, k, stride, pad, ACT[act], K, kpad, Cin, cout, cout, H * W * Cin,
-            Ho * Wo * cout, Ho * Wo * cout, 0, Ho, Wo, tile]
-    rec[0]["i"][:len(vals)] = vals
-    for j, t in enumerate((x, w_packed, bias, y, res, in_scale, w3, None, x3)):
-        rec[0]["p"][j] = 0 if t is None else t.data_ptr()
+    rec = conv_record((B, H, W, Cin), cout, k, stride, pad, act, x, w_packed, bias, y, res=res, in_scale=in_scale,
+                      w3=w3, x3=x3, tile=tile)
     check(lib().edgedet_plan_run(rec.ctypes.data_as(ctypes.c_void_p), 1, stream_handle()))
     return y
 

@@ -11,9 +11,11 @@ once into
     kind = csrc/records.hpp) that libedgedet.so runs
     directly or captures into a hipGraph replayed per batch.
 NativePlan is that plan on the Python side: the workspace as one torch allocation, the records
-resolved against it, and the named buffers.  Plan / conv_op below build records by hand for the
-unit tests of single kernels.  Nothing here computes detections: every FLOP runs in the HIP kernels
-of libedgedet.so.
+resolved against it, and the named buffers; ops.conv_record builds single records by hand for the
+unit tests of the kernels, and Plan strings such records together for the executor's tests (no
+lowering policy: no tile table, no switch).  The numpy pack helpers (fold_bn, pack_conv_weight, pack_dw_weight,
+split_bf16x3) restate the library's packer independently, for the tests that check it.  Nothing here
+computes detections: every FLOP runs in the HIP kernels of libedgedet.so.
 """
 import ctypes
 import os
@@ -23,8 +25,6 @@ import torch
 
 from . import ops
 
-ALIGN = 256
-
 # Conv math of the compute-bound conv tiles: "bf16x6" (fp32 GEMM as six bf16 partial products on the
 # bf16 matrix cores, error below one fp32 rounding per product; csrc/conv.hip) or "f32"
 # (v_mfma_f32_32x32x2_f32).  Override with EDGEDET_CONV_MATH=f32.
@@ -33,21 +33,10 @@ if CONV_MATH not in ("bf16x6", "f32"):
     raise ValueError(f"EDGEDET_CONV_MATH must be 'bf16x6' or 'f32', got {CONV_MATH!r}")
 
 
-# Measured tile per conv shape on gfx950 (tools/tune_conv.py); shapes not listed fall back to the
-# library's heuristic (csrc/conv.hip choose_tile).
-_TILES_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "conv_tiles_gfx950.json")
-# Pre-split conv inputs for the 256 x 128 bf16x6 tile (csrc/conv.hip split_act_kernel): one x3 scratch
-# per lane, sized for the largest input it serves; only where an input transform is fused (as the
-# library's lowering, csrc/lower.hip conv_op).
-CONV_TILES = {}
-if os.path.exists(_TILES_PATH) and os.environ.get("EDGEDET_CONV_TUNED", "1") == "1":
-    import json as _json
-    with open(_TILES_PATH) as _f:
-        CONV_TILES.update(_json.load(_f).get("tiles", {}))
-
-
 def conv_key(op):
-    """Shape key of a CONV op for the tuned tile table."""
+    """Shape key of a CONV op in the tuned tile table (data/conv_tiles_gfx950.json): what
+    tools/tune_conv.py writes and the library's lowering looks up (csrc/lower.hip conv_key;
+    tests/test_native_model.py holds the two to each other)."""
     i = op.i
     lin = int(i[7] == 1 and i[8] == 1 and i[9] == 1 and i[10] == 0)
     return ",".join(str(int(v)) for v in (i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7], i[9], lin,
@@ -78,50 +67,6 @@ def split_bf16x3(w):
 
 
 # ------------------------------------------------------------------------------ weights
-class WeightPack:
-    """Host-side collection of float32 arrays packed into one device blob."""
-
-    def __init__(self):
-        self.arrays = []
-        self.size = 0  # in floats
-        self.device_blob = None
-
-    def add_u16(self, arr):
-        """Add a uint16 array (bf16 bit patterns) of even length, stored bit-exact in the float blob."""
-        a = np.ascontiguousarray(arr, dtype=np.uint16).reshape(-1)
-        if a.size % 2:
-            a = np.concatenate([a, np.zeros(1, np.uint16)])
-        return self.add(a.view(np.float32))
-
-    def add(self, arr):
-        if isinstance(arr, np.ndarray) and arr.dtype == np.float32:
-            a = np.ascontiguousarray(arr).reshape(-1)
-        else:
-            a = np.ascontiguousarray(np.asarray(arr, dtype=np.float32)).reshape(-1)
-        off = self.size
-        self.arrays.append((off, a))
-        self.size = off + ((a.size + 63) // 64) * 64
-        return WRef(self, off, a.size)
-
-    def upload(self, device):
-        if self.device_blob is not None and self.device_blob.device == torch.device(device):
-            return self.device_blob
-        host = np.zeros(self.size, dtype=np.float32)
-        for off, a in self.arrays:
-            host[off:off + a.size] = a
-        self.device_blob = torch.from_numpy(host).to(device)
-        return self.device_blob
-
-
-class WRef:
-    def __init__(self, pack, off, n):
-        self.pack, self.off, self.n = pack, off, n
-        self.split = None  # WRef of the bf16x3 planes of a packed conv weight (conv_op p6)
-
-    def ptr(self):
-        return self.pack.device_blob.data_ptr() + 4 * self.off
-
-
 def fold_bn(w, gamma, beta, mean, var, eps):
     """Eval BatchNorm folded into the preceding bias-free conv (float64 math, float32 result)."""
     w = np.asarray(w, dtype=np.float64)
@@ -161,45 +106,6 @@ def _esize(dtype):
     return _ESIZE[dtype]
 
 
-class Buf:
-    """A carve-out of the plan arena (float32 unless dtype says otherwise)."""
-
-    def __init__(self, shape, dtype=torch.float32, name=""):
-        self.shape = tuple(int(s) for s in shape)
-        self.dtype = dtype
-        self.name = name
-        self.nbytes = int(np.prod(self.shape)) * _esize(dtype)
-        self.off = None
-        self.plan = None
-
-    def ptr(self):
-        return self.plan.arena.data_ptr() + self.off
-
-    def tensor(self):
-        n = int(np.prod(self.shape))
-        es = _esize(self.dtype)
-        flat = self.plan.arena[self.off:self.off + n * es].view(self.dtype)
-        return flat.view(self.shape)
-
-
-class BufView:
-    """A batch slice of a Buf: images [b0, b0 + n) of a buffer whose leading dimension is the batch
-    (the per-chain inputs / outputs of a batch-split plan)."""
-
-    def __init__(self, buf, b0, n):
-        self.buf, self.b0, self.n = buf, b0, n
-        per = buf.nbytes // buf.shape[0]
-        self.byte_off = b0 * per
-        self.shape = (n,) + tuple(buf.shape[1:])
-        self.dtype = buf.dtype
-
-    def ptr(self):
-        return self.buf.ptr() + self.byte_off
-
-    def tensor(self):
-        return self.buf.tensor()[self.b0:self.b0 + self.n]
-
-
 class Op:
     def __init__(self, kind, i=None, p=None, f=None, d=None, name="", lane=0):
         self.kind, self.name, self.lane = kind, name, lane
@@ -209,106 +115,33 @@ class Op:
         self.d = dict(d or {})
 
 
-class Plan:
-    """A lowered forward: ops + arena + weights; run() or run via a captured hipGraph."""
+# ------------------------------------------------------------------------------ native plans
+_DTYPES = {0: torch.float32, 1: torch.int32, 2: torch.int64, 3: torch.uint8, 4: torch.int16}
 
-    def __init__(self, weights, device):
-        self.weights = weights
-        self.device = torch.device(device)
-        self.ops = []
-        self.bufs = []
-        self.arena = None
-        self.records = None
-        self.graph = None
-        self.consts = []  # host arrays uploaded into the arena at finalize (anchors, ratios)
 
-    # building -----------------------------------------------------------------------------
-    def buf(self, shape, dtype=torch.float32, name=""):
-        b = Buf(shape, dtype, name)
-        b.plan = self
-        self.bufs.append(b)
-        return b
+class NativeBuf:
+    """A named carve-out of a NativePlan's workspace (edgedet_model_buffers)."""
 
-    def const(self, arr, dtype=torch.float32, name=""):
-        a = np.ascontiguousarray(arr)
-        b = self.buf(a.shape, dtype, name)
-        self.consts.append((b, a))
-        return b
+    def __init__(self, plan, name, offset, nbytes, dtype, shape):
+        # the workspace tensor, not the plan: no plan <-> buffer reference cycle, so a plan (its graph
+        # and workspace) is released when its last user drops it, at a known point, never by a
+        # garbage-collector pass on whatever thread triggers one (possibly while graphs are launching)
+        self.arena, self.name, self.off, self.nbytes = plan.arena, name, int(offset), int(nbytes)
+        self.dtype, self.shape = dtype, tuple(int(v) for v in shape)
 
-    def x3_scratch(self, n):
-        """The current lane's pre-split scratch, grown to at least n uint16 (ops of one lane run in
-        order on one stream, so one scratch serves all of them)."""
-        lane = getattr(self, "_lane", 0)
-        d = self.__dict__.setdefault("_x3", {})
-        b = d.get(lane)
-        if b is None:
-            b = d[lane] = self.buf((n,), torch.int16, name=f"x3.lane{lane}")
-        elif b.shape[0] < n:
-            b.shape, b.nbytes = (n,), 2 * n
-        return b
+    def ptr(self):
+        return self.arena.data_ptr() + self.off
 
-    def add(self, op):
-        if op.lane == 0 and getattr(self, "_lane", 0):
-            op.lane = self._lane
-        self.ops.append(op)
-        return op
+    def tensor(self):
+        es = _esize(self.dtype)
+        n = int(np.prod(self.shape))
+        return self.arena[self.off:self.off + n * es].view(self.dtype).view(self.shape)
 
-    # concurrency ---------------------------------------------------------------------------
-    def fork(self, nlanes):
-        """Side lanes 1..nlanes start after everything issued so far (independent branches)."""
-        self.ops.append(Op(ops.FORK, {0: nlanes}, name="fork"))
-        self._forked = nlanes
 
-    def lane(self, k):
-        """Issue the following ops on lane k (0 = the caller's stream)."""
-        self._lane = k
+class Records:
+    """An array of op records (`records`, with `graph` = None to start) that the library runs
+    directly or captures into a hipGraph."""
 
-    def wait(self, lane, on):
-        """Lane `lane` waits for everything issued so far on lane `on` (both forked, or 0)."""
-        self.ops.append(Op(ops.WAIT, {0: lane, 1: on}, name=f"wait{lane}<-{on}"))
-
-    def join(self):
-        self._lane = 0
-        self.ops.append(Op(ops.JOIN, {0: self._forked}, name="join"))
-        self._forked = 0
-
-    # finalizing ---------------------------------------------------------------------------
-    def finalize(self):
-        off = 0
-        for b in self.bufs:
-            b.off = off
-            off += (b.nbytes + ALIGN - 1) // ALIGN * ALIGN
-        self.arena = torch.zeros(max(off, ALIGN), dtype=torch.uint8, device=self.device)
-        self.weights.upload(self.device)
-        for b, a in self.consts:
-            b.tensor().copy_(torch.from_numpy(a).to(b.dtype))
-        rec = np.zeros(len(self.ops), dtype=ops.OP_DTYPE)
-        for k, op in enumerate(self.ops):
-            rec[k]["kind"] = op.kind
-            for j, v in op.i.items():
-                rec[k]["i"][j] = int(v)
-            rec[k]["i"][ops.LANE_FIELD] = op.lane
-            for j, v in op.p.items():
-                if v is None:
-                    rec[k]["p"][j] = 0
-                elif isinstance(v, (Buf, WRef, BufView)):
-                    rec[k]["p"][j] = v.ptr()
-                else:
-                    rec[k]["p"][j] = int(v)
-            for j, v in op.f.items():
-                rec[k]["f"][j] = float(v)
-            for j, v in op.d.items():
-                rec[k]["d"][j] = float(v)
-        self.records = rec
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        return self
-
-    @property
-    def arena_bytes(self):
-        return 0 if self.arena is None else self.arena.numel()
-
-    # running ------------------------------------------------------------------------------
     def run(self, stream=None):
         L = ops.lib()
         ops.check(L.edgedet_plan_run(self.records.ctypes.data_as(ctypes.c_void_p), len(self.records),
@@ -345,38 +178,8 @@ class Plan:
         except Exception:
             pass
 
-    def summary(self):
-        kinds = {}
-        for op in self.ops:
-            kinds[op.kind] = kinds.get(op.kind, 0) + 1
-        return {"ops": len(self.ops), "by_kind": kinds, "arena_MB": self.arena_bytes / 2 ** 20,
-                "weights_MB": self.weights.size * 4 / 2 ** 20}
 
-
-# ------------------------------------------------------------------------------ native plans
-_DTYPES = {0: torch.float32, 1: torch.int32, 2: torch.int64, 3: torch.uint8, 4: torch.int16}
-
-
-class NativeBuf:
-    """A named carve-out of a NativePlan's workspace (edgedet_model_buffers)."""
-
-    def __init__(self, plan, name, offset, nbytes, dtype, shape):
-        # the workspace tensor, not the plan: no plan <-> buffer reference cycle, so a plan (its graph
-        # and workspace) is released when its last user drops it, at a known point, never by a
-        # garbage-collector pass on whatever thread triggers one (possibly while graphs are launching)
-        self.arena, self.name, self.off, self.nbytes = plan.arena, name, int(offset), int(nbytes)
-        self.dtype, self.shape = dtype, tuple(int(v) for v in shape)
-
-    def ptr(self):
-        return self.arena.data_ptr() + self.off
-
-    def tensor(self):
-        es = _esize(self.dtype)
-        n = int(np.prod(self.shape))
-        return self.arena[self.off:self.off + n * es].view(self.dtype).view(self.shape)
-
-
-class NativePlan:
+class NativePlan(Records):
     """The library's plan of (model, B, H, W, u8): workspace, resolved records, named buffers."""
 
     def __init__(self, model, B, H, W, u8, device):
@@ -441,11 +244,6 @@ class NativePlan:
     def arena_bytes(self):
         return self.arena.numel()
 
-    run = Plan.run
-    capture = Plan.capture
-    replay = Plan.replay
-    __del__ = Plan.__del__
-
     def summary(self):
         kinds = {}
         for op in self.ops:
@@ -454,41 +252,107 @@ class NativePlan:
                 "weights_MB": self.weights.numel() / 2 ** 20}
 
 
-# ------------------------------------------------------------------------------ op helpers
-def conv_op(plan, x, x_shape, w, bias, cout, k, stride, pad, act, y, y_shape, K, Kpad, res=None, res_hw=None,
-            in_scale=None, y_pstride=None, y_bstride=None, y_off=0, x_pstride=None, x_bstride=None, tile=0,
-            name="", in_shift=None, in_relu=False):
-    """Build a CONV record (the numbered slots are rec::conv of csrc/records.hpp, the layout's home).
-    x_shape = (B, H, W, C) as laid out in x; y_shape = (B, Ho, Wo, Cout)."""
-    B, H, W, C = x_shape
-    _, Ho, Wo, _ = y_shape
-    assert Ho == (H + 2 * pad - k) // stride + 1 and Wo == (W + 2 * pad - k) // stride + 1, name
-    assert K == k * k * C, (name, K, k, C)
-    xp = C if x_pstride is None else x_pstride
-    yp = cout if y_pstride is None else y_pstride
-    rH, rW = res_hw if res_hw is not None else (Ho, Wo)
-    i = {0: B, 1: H, 2: W, 3: C, 4: Ho, 5: Wo, 6: cout, 7: k, 8: k, 9: stride, 10: pad, 11: ops.ACT[act], 12: K,
-         13: Kpad, 14: xp, 15: yp, 16: cout, 17: (H * W * xp if x_bstride is None else x_bstride),
-         18: (Ho * Wo * yp if y_bstride is None else y_bstride), 19: rH * rW * cout, 20: y_off, 21: rH, 22: rW,
-         23: tile, 24: 1 if in_relu else 0}
-    w3 = getattr(w, "split", None) if CONV_MATH == "bf16x6" else None
-    op = Op(ops.CONV, i, {0: x, 1: w, 2: bias, 3: y, 4: res, 5: in_scale, 6: w3, 7: in_shift}, name=name)
-    if not tile:
-        t = CONV_TILES.get(conv_key(op))
-        if t and (w3 is not None or t < 20):
-            op.i[23] = int(t)
-    if op.i[23] == 26:
-        # split-K accumulates into y: only for a dense output without activation or residual, zeroed
-        # by a MEMSET record right before the conv (another conv of the same shape key may not qualify)
-        dense = yp == cout and y_off == 0 and (y_bstride is None or y_bstride == Ho * Wo * cout)
-        if act is None and res is None and dense and w3 is not None:
-            plan.add(Op(ops.MEMSET, {0: B * Ho * Wo * cout * 4}, {0: y}, name=name + ".zero"))
-        else:
-            op.i[23] = 25
-    # only where an input transform is fused: the split pass then also takes the per-element GN / SE
-    # arithmetic out of the GEMM loop (measured: GN+ReLU head conv 1.83 -> 1.74 ms); for a plain input
-    # the extra pass costs more than the in-loop split (box head 2.48 -> 2.60 ms)
-    xf = in_scale is not None or in_shift is not None or in_relu
-    if xf and w3 is not None and C % 32 == 0 and op.i[23] in (0, 25):
-        op.p[8] = plan.x3_scratch(3 * B * H * W * C + 32)  # 32 leading zeros (csrc/conv.hip X3Z)
-    return plan.add(op)
+# ------------------------------------------------------------------------------ hand-built plans
+# Records put together by hand, for the executor's tests (tests/test_gpu_lanes.py: FORK / WAIT / JOIN
+# around plain convs).  No lowering policy lives here: a conv gets the tile its caller names (0 = the
+# kernel's own choice, csrc/conv.hip choose_tile), and nothing reads the tuned table or a switch.
+class WeightPack:
+    """Float32 arrays at 64-float boundaries of one device blob."""
+
+    def __init__(self):
+        self.arrays, self.size, self.device_blob = [], 0, None
+
+    def add(self, arr):
+        assert self.device_blob is None, "the pack is uploaded: its blob is fixed"
+        a = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
+        self.arrays.append((self.size, a))
+        ref = WRef(self, self.size)
+        self.size += (a.size + 63) // 64 * 64
+        return ref
+
+    def upload(self, device):
+        host = np.zeros(self.size, dtype=np.float32)
+        for off, a in self.arrays:
+            host[off:off + a.size] = a
+        self.device_blob = torch.from_numpy(host).to(device)
+
+
+class WRef:
+    def __init__(self, pack, off):
+        self.pack, self.off = pack, off
+
+    def ptr(self):
+        return self.pack.device_blob.data_ptr() + 4 * self.off
+
+
+class Buf:
+    """A float32 activation of a hand-built plan: its own allocation."""
+
+    def __init__(self, shape, device, name):
+        self.name, self.data = name, torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+
+    def ptr(self):
+        return self.data.data_ptr()
+
+    def tensor(self):
+        return self.data
+
+
+class Plan(Records):
+    """Records added one by one; `weights` is complete when the plan is made (uploaded here)."""
+
+    def __init__(self, weights, device):
+        self.weights, self.device, self.graph = weights, torch.device(device), None
+        weights.upload(self.device)
+        self.ops, self.bufs, self._recs, self._lane = [], [], [], 0
+
+    def buf(self, shape, name=""):
+        self.bufs.append(Buf(shape, self.device, name))
+        return self.bufs[-1]
+
+    def _append(self, rec, name):
+        self._recs.append(rec)
+        self.ops.append(Op(int(rec["kind"][0]), name=name, lane=int(rec["i"][0, ops.LANE_FIELD])))
+
+    def add(self, rec, name=""):
+        """One record, on the current lane."""
+        rec["i"][0, ops.LANE_FIELD] = self._lane
+        self._append(rec, name)
+
+    def _sync(self, kind, name, *ints):
+        """FORK / WAIT / JOIN: records of the caller's stream (lane 0) whatever the current lane."""
+        rec = np.zeros(1, dtype=ops.OP_DTYPE)
+        rec["kind"] = kind
+        rec["i"][0, :len(ints)] = ints
+        self._append(rec, name)
+
+    def fork(self, nlanes):
+        """Side lanes 1..nlanes start after everything issued so far (independent branches)."""
+        self._forked = nlanes
+        self._sync(ops.FORK, "fork", nlanes)
+
+    def lane(self, k):
+        """Issue the following records on lane k (0 = the caller's stream)."""
+        self._lane = k
+
+    def wait(self, lane, on):
+        """Lane `lane` waits for everything issued so far on lane `on` (both forked, or 0)."""
+        self._sync(ops.WAIT, f"wait{lane}<-{on}", lane, on)
+
+    def join(self):
+        self._lane = 0
+        self._sync(ops.JOIN, "join", self._forked)
+
+    def finalize(self):
+        self.records = np.concatenate(self._recs)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        return self
+
+
+def conv_op(plan, x, x_shape, w, bias, cout, k, stride, pad, act, y, y_shape, K, Kpad, tile=0, name=""):
+    """A plain CONV record (ops.conv_record) on the plan's current lane; x, y are Bufs, w, bias WRefs."""
+    assert x.data.shape == tuple(x_shape) and y.data.shape == tuple(y_shape), name
+    assert K == k * k * x_shape[3] and Kpad == (K + 31) // 32 * 32, (name, K, Kpad)
+    plan.add(ops.conv_record(x_shape, cout, k, stride, pad, act, x.ptr(), w.ptr(), bias.ptr(), y.ptr(), tile=tile),
+             name)

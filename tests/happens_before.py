@@ -13,7 +13,7 @@ Ordering is tracked with vector clocks (one per lane).  A plan is replayed many 
 the check also requires every record to be ordered before the end of the plan (joined into lane 0),
 so a replay never overlaps the previous one.
 
-Byte ranges come from the record fields (csrc/exec.hip's record layouts): the exact strided extents of
+Byte ranges come from the record fields (the layouts of csrc/records.hpp): the exact strided extents of
 CONV inputs / outputs / residuals (the SSDLite heads write map slices of the concatenated outputs,
 and the batch chains write batch slices of shared buffers), the dense extents of the depthwise /
 pooling records, and otherwise the named buffer holding the pointer (edgedet_model_buffers), cut to
@@ -26,7 +26,7 @@ from edgeml_amd import ops
 
 R, W, RW = "r", "w", "rw"
 
-# (kind) -> {pointer field: role}; the record layouts of csrc/exec.hip
+# (kind) -> {pointer field: role}; the record layouts of csrc/records.hpp
 ROLES = {
     ops.MEMSET: {0: W},
     ops.PREPROCESS: {0: R, 2: R, 1: W},

@@ -15,7 +15,6 @@ slack holds the same (NaN) pattern and the input's slack NaN, so a stray read po
 import ctypes
 import functools
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -171,16 +170,12 @@ def _run(name, tile, yv="dense", rv=None, xv="dense", se=False, presplit=False):
         rpar, _ = _parent(src.reshape(B, rH * rW, Cout), r_ps, r_bs, 0, CANARY)
     sc = d["sc"].to(DEV) if se else None
     x3 = torch.empty(3 * B * H * W * Cin + 32, dtype=torch.int16, device=DEV) if presplit else None
-    rec = np.zeros(1, dtype=ops.OP_DTYPE)
-    rec[0]["kind"] = ops.CONV
-    kpad = int(ops.lib().edgedet_conv_weight_k(k, k, Cin))
-    vals = [B, H, W, Cin, Ho, Wo, Cout, k, k, s, pad, ops.ACT[act], k * k * Cin, kpad, x_ps, y_ps, r_ps, x_bs,
-            y_bs, r_bs, y_off, rH, rW, tnum]
-    rec[0]["i"][:len(vals)] = vals
-    ptrs = (xpar, d["wp"], d["b"], ypar, rpar, sc, d["w3"] if x6 else None, None, x3)
-    for j, t in enumerate(ptrs):
-        # x / y / res point at the parent's element SLACK (256 bytes in: the alignment is kept)
-        rec[0]["p"][j] = 0 if t is None else t.data_ptr() + (4 * SLACK if j in (0, 3, 4) else 0)
+    # x / y / res point at the parent's element SLACK (256 bytes in: the alignment is kept)
+    inside = lambda t: None if t is None else t.data_ptr() + 4 * SLACK  # noqa: E731
+    rec = ops.conv_record((B, H, W, Cin), Cout, k, s, pad, act, inside(xpar), d["wp"], d["b"], inside(ypar),
+                          res=inside(rpar), in_scale=sc, w3=d["w3"] if x6 else None, x3=x3, x_pstride=x_ps,
+                          y_pstride=y_ps, res_pstride=r_ps, x_bstride=x_bs, y_bstride=y_bs, res_bstride=r_bs,
+                          y_off=y_off, res_hw=(rH, rW), tile=tnum)
     try:
         ops.check(ops.lib().edgedet_plan_run(rec.ctypes.data_as(ctypes.c_void_p), 1, ops.stream_handle()))
     finally:

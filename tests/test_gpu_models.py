@@ -90,8 +90,7 @@ def test_ssd_batch_chains_agree(ssd, monkeypatch):
     from edgeml_amd import native
     reps = {}
     for n in (1, 2):
-        monkeypatch.setenv("EDGEDET_SSD_CHAINS", str(n))  # read by the library's lowering
-        native.release("ssd", 16, 640, 640)
+        monkeypatch.setenv("EDGEDET_SSD_CHAINS", str(n))  # read by the library's lowering, part of its plan key
         model.plans.clear()
         plan = _run(model, imgs)
         assert plan.chains == n

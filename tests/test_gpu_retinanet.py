@@ -60,16 +60,9 @@ def test_conv_fused_groupnorm_relu_input(tile):
     wp = torch.from_numpy(pack_conv_weight(w.numpy())[0]).to(DEV)
     w3 = ops.split_bf16x3(wp) if tile in (0, 23, 25) else None
     import ctypes
-    Cin = Cout = 256
-    y = torch.empty((B, H, W, Cout), device=DEV)
-    K = 9 * Cin
-    rec = np.zeros(1, dtype=ops.OP_DTYPE)
-    rec[0]["kind"] = ops.CONV
-    vals = [B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 0, K, K, Cin, Cout, Cout, H * W * Cin, H * W * Cout, H * W * Cout, 0,
-            H, W, tile, 1]
-    rec[0]["i"][:len(vals)] = vals
-    for j, t in enumerate((xd, wp, b.to(DEV), y, None, sc, w3, sh)):
-        rec[0]["p"][j] = 0 if t is None else t.data_ptr()
+    y = torch.empty((B, H, W, 256), device=DEV)
+    rec = ops.conv_record((B, H, W, 256), 256, 3, 1, 1, None, xd, wp, b.to(DEV), y, in_scale=sc, w3=w3, in_shift=sh,
+                          tile=tile, in_relu=True)
     ops.check(ops.lib().edgedet_plan_run(rec.ctypes.data_as(ctypes.c_void_p), 1, ops.stream_handle()))
     err = (y.permute(0, 3, 1, 2).cpu() - ref).abs().max().item()
     assert err < 1e-4 * max(1.0, ref.abs().max().item()), err

@@ -311,7 +311,6 @@ def test_ssd_chain_split_covers_the_batch(monkeypatch):
     m = models.ssdlite320_mobilenet_v3_large()
     for B, n, want in [(32, 0, 2), (33, 0, 2), (10, 0, 1), (40, 4, 4), (24, 3, 3)]:
         monkeypatch.setenv("EDGEDET_SSD_CHAINS", str(n))
-        native.release("ssd", B, 320, 320)
         P = m.build_plan(B, 320, 320)
         parts = [P.buffer(f"backbone.features.0.13#{c}").shape[0] for c in range(P.chains)] if P.chains > 1 else [B]
         assert P.chains == want and sum(parts) == B and max(parts) - min(parts) <= 1

@@ -33,6 +33,9 @@ def built():
     return get
 
 
+FAKE_BASES = (0x7000000000, 0x8000000000)  # weights, workspace: records resolved against fixed addresses
+
+
 def _np(t):
     return t.detach().cpu().to(torch.float64).numpy()
 
@@ -175,15 +178,73 @@ def test_pack_rejects_bad_state_dict(built):
 
 def test_fused_block_lowering(built, monkeypatch):
     """The whole-block MBCONV lowering (default; EDGEDET_MB_BLOCK=0 turns it off) replaces blocks 0.2
-    and 0.3."""
+    and 0.3.  The switch is part of the library's plan key: flipping it, with no release in between,
+    never returns the plan lowered under the other setting, and flipping it back gives the first
+    plan's records again (resolved against fixed bases: each build_plan has its own arena)."""
     _, m = built("ssd")
-    B, H, W = 5, 300, 400  # a shape no other test lowers (the library caches plans per shape)
-    for v, n in (("1", 2), ("0", 0)):
+    B, H, W = 5, 300, 400
+    recs = []
+    for v, n in (("1", 2), ("0", 0), ("1", 2)):
         monkeypatch.setenv("EDGEDET_MB_BLOCK", v)
-        native.release("ssd", B, H, W)
         P = m.build_plan(B, H, W)
         assert sum(op.kind == ops.MBCONV for op in P.ops) == n
+        recs.append(native.records("ssd", B, H, W, *FAKE_BASES))
+        assert sum(recs[-1]["kind"] == ops.MBCONV) == n
+    assert recs[0].tobytes() == recs[2].tobytes() and recs[0].tobytes() != recs[1].tobytes()
     native.release("ssd", B, H, W)
+
+
+def test_equivalent_chain_settings_share_a_lowering(monkeypatch):
+    """EDGEDET_SSD_CHAINS unset, 0 and 2 mean the same (two chains at most): byte-identical records."""
+    recs = []
+    for v in (None, "0", "2"):
+        if v is None:
+            monkeypatch.delenv("EDGEDET_SSD_CHAINS", raising=False)
+        else:
+            monkeypatch.setenv("EDGEDET_SSD_CHAINS", v)
+        recs.append(native.records("ssd", 32, 320, 320, *FAKE_BASES))
+        assert sum(recs[-1]["kind"] == ops.FORK) == 1
+    assert recs[0].tobytes() == recs[1].tobytes() == recs[2].tobytes()
+    monkeypatch.setenv("EDGEDET_SSD_CHAINS", "1")
+    assert sum(native.records("ssd", 32, 320, 320, *FAKE_BASES)["kind"] == ops.FORK) == 0
+    native.release("ssd", 32, 320, 320)
+
+
+def test_tuner_key_is_the_library_key(monkeypatch):
+    """tools/tune_conv.py writes the table under plan.conv_key(record) and the library looks its own
+    key up (csrc/lower.hip conv_key): they must be the same string.  For every CONV record of two
+    product lowerings, with and without the table: a key the table holds with tile t lowers to t
+    (39 where t is 25: the Cout = 256 rule; 25 where t is 26: a split-K tile the layer does not
+    qualify for), any other key to the same tile either way.  The grouped head convs, whose tile the
+    lowering sets itself (non-zero without the table too), never consult the table: the same tile
+    either way, and no hit."""
+    import json
+    import os
+    from edgeml_amd import plan as plan_mod
+    with open(os.path.join(os.path.dirname(os.path.abspath(plan_mod.__file__)), "data", "conv_tiles_gfx950.json")) as f:
+        table = json.load(f)["tiles"]
+    for kind in ("ssd", "faster_rcnn"):
+        convs = {}
+        for v in ("1", "0"):
+            monkeypatch.setenv("EDGEDET_CONV_TUNED", v)
+            # MEMSET records come and go with tile 26; the convs keep their order
+            recs = native.records(kind, 1, 640, 640, *FAKE_BASES)
+            convs[v] = [plan_mod.Op(ops.CONV, dict(enumerate(r["i"])), {j: int(a) or None for j, a in enumerate(r["p"])})
+                        for r in recs[recs["kind"] == ops.CONV]]
+        assert len(convs["1"]) == len(convs["0"])
+        hits = 0
+        for n, (op, op0) in enumerate(zip(convs["1"], convs["0"])):
+            key, tile, untuned = plan_mod.conv_key(op), op.i[ops.CONV_TILE], op0.i[ops.CONV_TILE]
+            assert key == plan_mod.conv_key(op0)
+            if key in table and not untuned:
+                t = int(table[key])
+                assert tile == t or (t == 25 and tile == 39) or (t == 26 and tile == 25), (n, key, t, tile)
+                hits += 1
+            else:
+                assert tile == untuned, (n, key, tile, untuned)
+        print(f"{kind}: {hits} of {len(convs['1'])} convs in the table")
+        assert hits >= 20
+        native.release(kind, 1, 640, 640)
 
 
 def test_model_records_entry_resolves_external_pointers(built):
@@ -192,7 +253,7 @@ def test_model_records_entry_resolves_external_pointers(built):
     _, m = built("faster_rcnn")
     B, H, W = 1, 480, 640
     ext = [0x10000000 * (k + 1) for k in range(5)]
-    rec = native.records("faster_rcnn", B, H, W, 0x7000000000, 0x8000000000, 91, True, False, images=ext[0],
+    rec = native.records("faster_rcnn", B, H, W, *FAKE_BASES, 91, True, False, images=ext[0],
                          outputs=tuple(ext[1:]))
     P = m.build_plan(B, H, W)
     assert len(rec) == len(P.records) and (rec["kind"] == P.records["kind"]).all()

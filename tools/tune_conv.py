@@ -5,9 +5,10 @@
 Each CONV record of a lowered plan is launched alone on its own buffers (arena filled with N(0, 0.5)
 values: timing on all-zero data would read high, MI355X_MICROARCH.md "DVFS") with every tile id the
 library accepts for it (csrc/conv.hip conv_launch; variants that refuse the shape are skipped), HIP
-events around the reps.  The table maps plan.conv_key(record) -> tile; plan.conv_op applies it, so
-the choice is deterministic across runs (csrc/conv.hip choose_tile remains the fallback for shapes
-not in the table).
+events around the reps.  The table maps plan.conv_key(record) -> tile; the library's lowering
+(csrc/lower.hip conv_op) looks the same key up, so the choice is deterministic across runs
+(csrc/conv.hip choose_tile remains the fallback for shapes not in the table).  "auto" is that
+fallback: the record with 0 written into its tile slot.
 """
 import argparse
 import ctypes
@@ -82,8 +83,7 @@ def main():
     ap.add_argument("--models", default="ssd,frcnn,retinanet")
     ap.add_argument("--out", default=os.path.join(ROOT, "edgeml-object-detection_amd", "data", "conv_tiles_gfx950.json"))
     a = ap.parse_args()
-    from edgeml_amd import models, plan as plan_mod
-    plan_mod.CONV_TILES.clear()  # measure the library's own choice as "auto"
+    from edgeml_amd import models
     # re-tune the shapes of the given models, keep the other entries of the existing table
     table, log, done = {}, [], set()
     if os.path.exists(a.out):
