@@ -1913,7 +1913,9 @@ __global__ void __launch_bounds__(NT) unit_nms_kernel(const float* __restrict__ 
 }
 
 // ================================================================ per-image merge
-// Kept lists [B][S][kmax] -> top N by (score desc, tiebreak asc), boxes rescaled by ratio.
+// Kept lists [B][S][kmax] -> top N by (score desc, tiebreak asc), boxes rescaled by ratio.  Exact for any
+// number of equal scores: when the keys above the N-th score T and all ties at T fit the KC-entry list
+// they are sorted by (score, tiebreak) and cut; otherwise the ties are chosen by tiebreak first.
 
 template <int NT, int KC, int PER>
 __global__ void __launch_bounds__(NT) merge_topk_kernel(MergeParams P) {
@@ -1944,6 +1946,10 @@ __global__ void __launch_bounds__(NT) merge_topk_kernel(MergeParams P) {
         }
         return lo * P.kmax + (i - pre[lo]);
     };
+    auto fkey = [&](int i, uint32_t& k) -> bool {
+        k = float_key(P.score[base_off + flat(i)]);
+        return true;
+    };
     int m0;
     if (n <= NT * PER) {
         // all record offsets first (LDS searches), then the global loads back to back
@@ -1966,13 +1972,28 @@ __global__ void __launch_bounds__(NT) merge_topk_kernel(MergeParams P) {
         // every key > T plus all ties (up to capacity); ties are then ordered by tiebreak
         m0 = select_topk_regs<NT, PER>(kr, P.N, KC, S.keys, S.wsum, S.misc, true);
     } else {
-        auto fkey = [&](int i, uint32_t& k) -> bool {
-            k = float_key(P.score[base_off + flat(i)]);
-            return true;
-        };
         const uint32_t T = radix_select<NT>(n, P.N, fkey, S.hist, S.misc);
         const bool take_all = S.misc[1] <= P.N;
         m0 = compact<NT>(n, T, take_all, KC, KC, fkey, S.keys, S.wsum);
+    }
+    if (m0 >= KC && n > P.N) {
+        // The list is full, so keys > T plus the ties at T may not all have fitted, and what was dropped
+        // went by candidate position, not by tiebreak (on the radix path a key > T of a later batch may
+        // be among it).  Select again, exactly, in two steps: the G < N keys > T first (they always fit),
+        // then among the candidates equal to T the N - G with the smallest tiebreak (a second select on
+        // ~tb; tiebreaks are unique per image, so it takes exactly N - G).  G + (N - G) = N <= KC.
+        const uint32_t T = radix_select<NT>(n, P.N, fkey, S.hist, S.misc);
+        const int need = S.misc[5];  // ties at T that belong to the top N (n > N: never take-all)
+        const int g = compact<NT>(n, T, false, 0, KC, fkey, S.keys, S.wsum);
+        auto ftie = [&](int i, uint32_t& k) -> bool {
+            const int f = flat(i);
+            k = 0xffffffffu - P.tb[base_off + f];
+            return float_key(P.score[base_off + f]) == T;
+        };
+        const uint32_t T2 = radix_select<NT>(n, need, ftie, S.hist, S.misc);
+        const bool all2 = S.misc[1] <= need;
+        const int budget2 = S.misc[5];
+        m0 = g + compact<NT>(n, T2, all2, budget2, KC - g, ftie, S.keys + g, S.wsum);
     }
     // candidate indices must be recovered before pre[] (aliasing aux) is overwritten
     unsigned long long* tmp = S.mask;

@@ -97,8 +97,9 @@ def rpn(feats, sd, image_shapes, padded_size):
     return rpn_filter(*rpn_head(feats, sd, padded_size), image_shapes)
 
 
-def rpn_filter(objs, dels, anchors, image_shapes):
-    """RegionProposalNetwork.filter_proposals over the head outputs of rpn_head."""
+def rpn_filter(objs, dels, anchors, image_shapes, with_scores=False):
+    """RegionProposalNetwork.filter_proposals over the head outputs of rpn_head.  with_scores: per image
+    (proposals, scores) instead of the proposals alone."""
     out = []
     for n in range(objs[0].shape[0]):
         bl, sl, ll = [], [], []
@@ -117,7 +118,7 @@ def rpn_filter(objs, dels, anchors, image_shapes):
         boxes, scores, lvls = boxes[keep], scores[keep], lvls[keep]
         keep = torch.from_numpy(tv_ops.batched_nms(boxes.numpy(), scores.numpy(), lvls.numpy(), RPN_NMS))
         keep = keep[:RPN_POST_NMS]
-        out.append(boxes[keep])
+        out.append((boxes[keep], scores[keep]) if with_scores else boxes[keep])
     return out
 
 
