@@ -20,8 +20,14 @@ distributions (Kaiming-uniform weights, PyTorch's default bias and BatchNorm ini
 torch's global RNG, whose stream cannot be reproduced here; dropout masks come from a
 counter-based hash.  Parity: with dropout off, a fit equals the oracle (oracle/estimator.py,
 torch CPU) within fp32 rounding; with dropout on it is the same algorithm with another random
-stream (tests/test_gpu_estimator.py).  regression.py's sklearn models and hidden-layer feature
-maps of the external YOLOv5 (stages 0-23) are out of scope.
+stream (tests/test_gpu_estimator.py).
+
+--model LR | EN | BR | KNR runs regression.py's LinearRegression, ElasticNet, BayesianRidge and
+KNeighborsRegressor (behind fit_model's StandardScaler, float64) through edgeml_amd.regress
+(csrc/regress.hip): estimate<k>.npz goes to <save_dir> itself (regression.py:447-448) and,
+with --model-dir, wts<k>.pickle holds plain numpy data instead of sklearn objects.  SGD, RFR, GBR (random
+streams), SVR, LSVR (libsvm / liblinear dual solvers) and the hidden-layer feature maps of the external
+YOLOv5 (stages 0-23) are out of scope; the CLI exits naming what is built.
 """
 import argparse
 import ctypes
@@ -222,24 +228,75 @@ def load_stage24(data_dir):
                      for im in images]) if images else np.zeros((0, 0))
 
 
+REGRESSORS = ("LR", "EN", "BR", "KNR")  # edgeml_amd.regress
+NOT_BUILT = ("SGD", "SVR", "LSVR", "RFR", "GBR")
+
+
+def check_model(opts):
+    """Refuse what is not built, naming what is."""
+    built = "--model CNN, LR (Linear Regression), EN (Elastic Net), BR (Bayesian Ridge) or KNR (K-nearest Neighbors)"
+    if opts.stage != 24:
+        raise SystemExit(f"edgeml_amd.estimator runs regression.py on the stage-24 output features ({built}, "
+                         "--stage 24); the YOLOv5 hidden-layer maps of stages 0-23 have no producer here")
+    if opts.model != "CNN" and opts.model not in REGRESSORS:
+        why = ("SGD, RFR and GBR draw random streams that cannot be reproduced, SVR and LSVR need the libsvm / "
+               "liblinear dual solvers" if opts.model in NOT_BUILT else f"'{opts.model}' is no model of regression.py")
+        raise SystemExit(f"edgeml_amd.estimator builds {built} on the stage-24 output features; {why}: "
+                         f"--model {opts.model} is not built")
+
+
+def fold_targets(reward, split, normalize, dtype):
+    """regression.py:436-441: per-fold targets [k, N], normalised against the fold's training set."""
+    y = np.zeros(split.shape, dtype)
+    for cv_idx, val_mask in enumerate(split):
+        tr_r, va_r = reward[~val_mask], reward[val_mask]
+        if normalize:
+            tr_r, va_r = normalize_rewards(tr_r, va_r)
+        y[cv_idx, ~val_mask], y[cv_idx, val_mask] = tr_r, va_r
+    return y
+
+
+def main_regressor(opts, features, reward, split):
+    """--model LR | EN | BR | KNR (regression.py:80-117, 214-217, 447-448): estimate{k}.npz in save_dir itself
+    and, with --model-dir, wts{k}.pickle holding plain numpy data (not the reference's sklearn objects)."""
+    import pickle
+    import sys
+
+    from . import regress
+    y = fold_targets(reward, split, opts.normalize, np.float64)
+    results, info = regress.FITS[opts.model](features, y, split)
+    if opts.model == "LR":
+        for f, r in enumerate(info["min_ratio"]):
+            if r < regress.LR_WARN_RATIO:
+                print(f"warning: fold {f + 1}: the smallest kept eigenvalue of Z^T Z is {r:.3e} of the largest "
+                      f"(rank {info['rank'][f]}): the least-squares solution is ill-conditioned", file=sys.stderr)
+    for cv_idx, val_mask in enumerate(split):
+        r = results[cv_idx]
+        tr_mse = float(np.mean((y[cv_idx, ~val_mask] - r["train_est"]) ** 2))
+        va_mse = float(np.mean((y[cv_idx, val_mask] - r["val_est"]) ** 2)) if val_mask.any() else float("nan")
+        print(f"fold {cv_idx + 1}: Trained {regress.NAMES[opts.model]} model with training MSE: {tr_mse:.3f}, "
+              f"validation MSE: {va_mse:.3f}")
+        save_result(opts.save_dir, r, cv_idx)
+        if opts.model_dir != "":
+            Path(opts.model_dir).mkdir(parents=True, exist_ok=True)
+            with open(os.path.join(opts.model_dir, f"wts{cv_idx + 1}.pickle"), "wb") as f:
+                pickle.dump(regress.model_data(opts.model, info, cv_idx), f)
+    return results, info
+
+
 def main(opts):
-    if opts.model != "CNN" or opts.stage != 24:
-        raise SystemExit("edgeml_amd.estimator runs regression.py's CNN estimator on the stage-24 output features "
-                         "(--model CNN --stage 24); the sklearn models and YOLOv5 hidden-layer maps are not built")
+    check_model(opts)
     features = load_stage24(opts.data_dir)
     with np.load(opts.reward_path, allow_pickle=False) as z:
         reward = z["reward"]
     assert len(features) == len(reward), "Inconsistent number of feature maps and offloading rewards."
     split = np.load(opts.split_path, allow_pickle=False)
     assert len(reward) == split.shape[1], "Inconsistent number of data points from the dataset and the split."
+    if opts.model in REGRESSORS:
+        return main_regressor(opts, features, reward, split)
     cnn = CNNOpt(weight=opts.weight and opts.normalize)
     save_best, save_last = parse_path(opts.save_dir)
-    y = np.zeros(split.shape, np.float32)  # per-fold targets (normalised against the fold's training set)
-    for cv_idx, val_mask in enumerate(split):
-        tr_r, va_r = reward[~val_mask], reward[val_mask]
-        if opts.normalize:
-            tr_r, va_r = normalize_rewards(tr_r, va_r)
-        y[cv_idx, ~val_mask], y[cv_idx, val_mask] = tr_r, va_r
+    y = fold_targets(reward, split, opts.normalize, np.float32)  # normalised against the fold's training set
     t0 = time.perf_counter()
     best, last, info = fit_folds(features, y, split, cnn, seed=opts.seed)  # every fold in one launch
     print(f"trained {len(split)} folds x {cnn.max_epoch} epochs in {time.perf_counter() - t0:.2f} s")

@@ -55,6 +55,9 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_mlp_state_size", "edgedet_mlp_fit", "edgedet_mlp_predict",
            "edgedet_dcsb_fit", "edgedet_svm_workspace_size", "edgedet_svm_fit", "edgedet_svm_hessian",
            "edgedet_svm_decision",
+           "edgedet_reg_workspace_size", "edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh",
+           "edgedet_reg_fit_lr", "edgedet_reg_fit_en", "edgedet_reg_fit_br", "edgedet_reg_predict",
+           "edgedet_knn_fit_predict",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
            "edgedet_model_prepare_host", "edgedet_model_forward", "edgedet_model_max_detections",
            "edgedet_model_records", "edgedet_ssdlite_workspace_size", "edgedet_ssdlite_forward",
@@ -138,6 +141,21 @@ def lib():
     L.edgedet_svm_hessian.argtypes = [_vp, _i64, _vp, _i64, _vp, _vp, _vp]
     L.edgedet_svm_decision.argtypes = [_vp, _i64, _i64, _vp, _i32, _vp, _vp]
     for name in ("edgedet_dcsb_fit", "edgedet_svm_fit", "edgedet_svm_hessian", "edgedet_svm_decision"):
+        getattr(L, name).restype = ctypes.c_int
+    L.edgedet_reg_workspace_size.argtypes = [_i32, _i64, _i64, _i64]
+    L.edgedet_reg_workspace_size.restype = _i64
+    L.edgedet_reg_scaler.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]
+    L.edgedet_reg_gram.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_reg_eigh.argtypes = [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_reg_fit_lr.argtypes = [_vp, _i64, _i32, _vp, _vp, _dbl, _vp, _vp, _vp, _vp]
+    L.edgedet_reg_fit_br.argtypes = [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp,
+                                     _vp, _vp, _vp]
+    L.edgedet_reg_fit_en.argtypes = [_vp, _i64, _vp, _vp, _i32, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_reg_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp]
+    L.edgedet_knn_fit_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp,
+                                          _vp, _vp]
+    for name in ("edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh", "edgedet_reg_fit_lr",
+                 "edgedet_reg_fit_br", "edgedet_reg_fit_en", "edgedet_reg_predict", "edgedet_knn_fit_predict"):
         getattr(L, name).restype = ctypes.c_int
     _u64 = ctypes.c_uint64
     L.edgedet_model_weights_size.argtypes = [_i32, _i32, _i32]

@@ -411,6 +411,70 @@ int edgedet_svm_hessian(const double* x, int64_t Dp, const int32_t* idx, int64_t
 int edgedet_svm_decision(const double* x, int64_t N, int64_t Dp, const double* v, int32_t folds, double* out,
                          void* stream);
 
+/* ------------------------------------------------------------------ estimator regressors (regression.py) */
+/*
+ * regression.py's LinearRegression, ElasticNet, BayesianRidge and KNeighborsRegressor behind fit_model's
+ * StandardScaler (:38-77), float64, every cross-validation fold in flight (csrc/regress.hip).  Common
+ * arguments: x [N][D] the raw features (1 <= D <= 255), y [F][N] the target of every row under every fold,
+ * fold f trains on rows tr_idx[tr_off[f] .. tr_off[f+1]) (tr_idx null: on rows tr_off[f] .. tr_off[f+1]
+ * themselves); tr_off_host is the host copy of the device array tr_off [F + 1].  Dp = D + 1 rounded up to
+ * a multiple of 16.  Every function checks its shapes on the host and returns 0 or a negative error code
+ * (edgedet_last_error); iterative solvers report a status per fold.
+ *
+ * edgedet_reg_workspace_size: bytes of the workspace of edgedet_reg_eigh (N = total_rows = 0) or of
+ * edgedet_knn_fit_predict (total_rows = tr_off[F]); < 0 on bad sizes.
+ */
+int64_t edgedet_reg_workspace_size(int32_t folds, int64_t D, int64_t N, int64_t total_rows);
+/* StandardScaler.fit per fold: mean [F][D], scale [F][D] = sqrt(population variance), 1 for a column that
+ * sklearn's _is_constant_feature calls constant (var <= n eps var + (n mean eps)^2); ymean [F] the mean of
+ * the fold's training targets (0 when y is null). */
+int edgedet_reg_scaler(const double* x, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
+                       const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, double* mean, double* scale,
+                       double* ymean, void* stream);
+/* G [F][Dp][Dp] = Z~^T Z~ over the fold's training rows by the fp64 matrix instruction, both triangles
+ * written: Z~ = ((x - mean) * (1 / scale), y - ymean, 0 ...), so G[:D,:D] = Z^T Z, G[:D,D] = Z^T yc and
+ * G[D,D] = yc^T yc (y null: that column is zero).  With folds = 1 and tr_idx null it is the unit operator
+ * for one matrix. */
+int edgedet_reg_gram(const double* x, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
+                     const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, const double* mean,
+                     const double* scale, const double* ymean, double* G, void* stream);
+/* Symmetric eigendecomposition of G[f][:D,:D] (cyclic parallel Jacobi, one workgroup per fold): lam [F][D]
+ * the eigenvalues clamped at 0 in the solver's order, vt [F][D][D] with row i the eigenvector of lam[i].
+ * Iterates until the off-diagonal norm is <= D eps |G|_F; offnorm [F][2] = {the final off-diagonal norm,
+ * that threshold}, sweeps [F], status [F]: 0 ok, 1 not converged in max_sweeps. */
+int edgedet_reg_eigh(const double* G, int64_t D, int32_t folds, void* ws, int64_t ws_bytes, int32_t max_sweeps,
+                     double* lam, double* vt, int32_t* sweeps, int32_t* status, double* offnorm, void* stream);
+/* LinearRegression: coef [F][D] = V+ diag(1 / lam+) V+^T Z^T yc over the eigenvalues lam > tau max(lam), the
+ * minimum-norm least-squares solution; rank [F] their count, min_ratio [F] the smallest kept lam / max(lam). */
+int edgedet_reg_fit_lr(const double* G, int64_t D, int32_t folds, const double* lam, const double* vt, double tau,
+                       double* coef, int32_t* rank, double* min_ratio, void* stream);
+/* BayesianRidge.fit (more training rows than features): sklearn's fixed-point loop in the eigenbasis, at
+ * most max_iter iterations, stopped when sum |coef_old - coef| < tol (not tested on the first); coef [F][D],
+ * hyper [F][2] = {alpha_, lambda_}, n_iter [F]. */
+int edgedet_reg_fit_br(const double* G, int64_t D, const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds,
+                       const double* lam, const double* vt, double alpha_1, double alpha_2, double lambda_1,
+                       double lambda_2, double tol, int32_t max_iter, double* coef, double* hyper, int32_t* n_iter,
+                       void* stream);
+/* ElasticNet(alpha, l1_ratio < 1): covariance-form cyclic coordinate descent on Q = Z^T Z / n, stopped when
+ * the optimality residual |z|_2 <= tol, tol = tol_abs when > 0, otherwise tol_rel |Z^T yc / n|_inf.
+ * coef [F][D], res [F][2] = {|z|, tol}, sweeps [F], status [F]: 0 ok, 1 not converged in max_sweeps. */
+int edgedet_reg_fit_en(const double* G, int64_t D, const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds,
+                       double alpha, double l1_ratio, double tol_rel, double tol_abs, int32_t max_sweeps, double* coef,
+                       double* res, int32_t* sweeps, int32_t* status, void* stream);
+/* out [F][N] = ((x - mean) * (1 / scale)) . coef + ymean for every row under every fold's model. */
+int edgedet_reg_predict(const double* x, int64_t N, int64_t D, const double* mean, const double* scale,
+                        const double* coef, const double* ymean, int32_t folds, double* out, void* stream);
+/* KNeighborsRegressor(n_neighbors = k), brute force on the standardised rows: every row of the dataset is a
+ * query against its fold's training rows.  Squared distances |a|^2 + |b|^2 - 2 a.b (clamped at 0) by the
+ * fp64 matrix instruction, an exact k-smallest selection with ties at the k-th distance resolved to the
+ * lowest training position; nbr [F][N][k] the neighbours' positions within the fold's training list in
+ * ascending order, est [F][N] the mean of their targets summed in that order.  1 <= k <= every fold's
+ * training rows. */
+int edgedet_knn_fit_predict(const double* x, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
+                            const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, const double* mean,
+                            const double* scale, int32_t k, void* ws, int64_t ws_bytes, double* est, int32_t* nbr,
+                            void* stream);
+
 /* ------------------------------------------------------------------ image ingest (read_image) */
 /*
  * torchvision.io.read_image(path, ImageReadMode.RGB) of detect.py:55-58 for baseline JPEGs, split
