@@ -11,6 +11,9 @@ Reads <data_dir>/<image>/stage24_output_features.npy (edgeml_amd.features writes
 npz (edgeml_amd.reward) and the k-fold split (k, N) bool; writes estimate<k>.npz {train_est,
 val_est, train_time, val_time} into <save_dir>_best and <save_dir>_last, as regression.py:438-446
 does through lib/utils.py parse_path / save_result (test.py / edgeml_amd.evaluate consume them).
+With --model-dir DIR it also writes DIR_best/wts<k>.pth and DIR_last/wts<k>.pth (regression.py:261,
+350-352): a torch.save'd dict of the MLP's tensors under EdgeDetectionNet's state-dict names, the
+estimator file edgeml_amd.offload takes.
 
 Semantics follow regression.py:220-355 (CNNOpt defaults: lr 5e-3, gamma 0.5 at epochs 60/75/90,
 weight decay 5e-5, 100 epochs, batch 64 in dataset order, linear [d0, 16, 16, 16, 16, 1]) with
@@ -304,7 +307,19 @@ def main(opts):
         print(f"fold {cv_idx + 1}: best test loss {info['test_loss'][cv_idx].min():.6f}")
         save_result(save_best, best[cv_idx], cv_idx)
         save_result(save_last, last[cv_idx], cv_idx)
+    if opts.model_dir != "":  # regression.py:261, 350-352
+        for path, states in zip(parse_path(opts.model_dir), (info["best_state"], info["last_state"])):
+            for cv_idx in range(len(split)):
+                save_state(path, info["spec"], states[cv_idx], cv_idx)
     return best, last
+
+
+def save_state(path, spec, state, index):
+    """wts<k>.pth: the MLP's tensors under EdgeDetectionNet's state-dict names (MlpSpec.unpack), what
+    edgeml_amd.offload loads."""
+    Path(path).mkdir(parents=True, exist_ok=True)
+    named = {k: torch.from_numpy(np.array(v, dtype=np.float32)) for k, v in spec.unpack(np.asarray(state)).items()}
+    torch.save(named, os.path.join(path, f"wts{index + 1}.pth"))
 
 
 def getargs(argv=None):

@@ -144,7 +144,7 @@ class _Detector:
     INFLIGHT = 2  # batches on the device at once in run_batches (measured best on MI355X: bench --inflight)
 
     @torch.no_grad()
-    def run_batches(self, batches, inflight=None, raw=False):
+    def run_batches(self, batches, inflight=None, raw=False, post=None):
         """Yield (tag, [(boxes, scores, labels) host numpy arrays per image]) for each (tag, images) of
         `batches`, in order, with up to `inflight` batches on the device at once (raw=True: yield
         (tag, counts [B], boxes [B,K,4], scores [B,K], labels [B,K]) padded host arrays instead, the
@@ -156,7 +156,15 @@ class _Detector:
         contract's float [3,H,W] tensors or the decoded uint8 [3,H,W] images (detect.py:57), which
         cross PCIe as bytes (4x fewer than float) and are divided by 255 on the device, bit-identical
         to the host's `image / 255` (detect.py:58).  Same arithmetic as __call__ (same plan
-        lowering, same kernels, replayed from a hipGraph per slot)."""
+        lowering, same kernels, replayed from a hipGraph per slot).
+
+        post: a callable post(plan, slot, stream, tag) run on the slot's stream after the batch's
+        replay and result copies are enqueued (the stream is current).  It may enqueue kernels that read
+        the plan's buffers and copies to the host, and leaves what the caller should get in
+        slot["post"] (buffers it keeps on the slot dict are its own to reuse: a slot is reused only
+        after its batch has been yielded).  Each yielded tuple then ends with that value, pinned host
+        tensors in it (top level of a dict, or the value itself) copied to numpy arrays once the batch
+        is done.  With post=None nothing changes."""
         if self.device is None:
             self.to("cuda")
         n = max(1, int(inflight or self.INFLIGHT))
@@ -204,12 +212,18 @@ class _Detector:
             lap("results")
             sl["src"] = None
             if raw:
-                return tag, sl["count"].numpy().copy(), sl["box"].numpy().copy(), sl["score"].numpy().copy(), \
-                    sl["label"].numpy().copy()
-            counts = sl["count"].tolist()
-            box, score, label = sl["box"].numpy(), sl["score"].numpy(), sl["label"].numpy()
-            return tag, [(box[j, :counts[j]].copy(), score[j, :counts[j]].copy(), label[j, :counts[j]].copy())
-                         for j in range(B)]
+                res = (tag, sl["count"].numpy().copy(), sl["box"].numpy().copy(), sl["score"].numpy().copy(),
+                       sl["label"].numpy().copy())
+            else:
+                counts = sl["count"].tolist()
+                box, score, label = sl["box"].numpy(), sl["score"].numpy(), sl["label"].numpy()
+                res = (tag, [(box[j, :counts[j]].copy(), score[j, :counts[j]].copy(), label[j, :counts[j]].copy())
+                             for j in range(B)])
+            if post is None:
+                return res
+            host = lambda v: v.numpy().copy() if torch.is_tensor(v) and not v.is_cuda else v  # noqa: E731
+            extra = sl.pop("post", None)
+            return res + ({k: host(v) for k, v in extra.items()} if isinstance(extra, dict) else host(extra),)
 
         def emit(item):
             r = collect(*item)
@@ -280,6 +294,8 @@ class _Detector:
                 sl["box"].copy_(plan.out_box.tensor(), non_blocking=True)
                 sl["score"].copy_(plan.out_score.tensor(), non_blocking=True)
                 sl["label"].copy_(plan.out_label.tensor(), non_blocking=True)
+                if post is not None:
+                    post(plan, sl, stream, tag)
                 sl["done"].record(stream)
             pending.append((tag, sl, B))
             while len(pending) >= n:

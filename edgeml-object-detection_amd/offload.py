@@ -1,0 +1,421 @@
+"""The offloading cascade itself: the weak detector on every image, a reward estimate per image from the
+weak detector's own output, and the strong detector only on the images whose estimate clears the
+threshold (the policy test.py:30-42 simulates on saved files, run for real in one process).
+
+    python -m edgeml_amd.offload img_dir save_dir --estimator WTS (--ratio R --estimates EST_DIR | --threshold T)
+           [--fold 1] [--k 25] [--dataset coco|voc] [--weak ssd] [--strong faster_rcnn]
+           [--weak-path P] [--strong-path P] [--weak-dir DIR] [--weak-batch N] [--strong-batch N]
+           [--decode gpu|host]
+
+WTS is a trained estimator: wts<fold>.pickle as `edgeml_amd.estimator --model LR|EN|BR --model-dir` writes
+it (plain numpy mean, scale, coef, intercept), or wts<fold>.pth as `--model CNN --model-dir` writes it (the
+MLP's tensors under EdgeDetectionNet's state-dict names; the layer widths are read from the weight
+shapes).  A KNR file is refused: it holds no training rows.  The threshold is --threshold, or test.py:35
+on EST_DIR/estimate<fold>.npz: train_est[argsort(-train_est)[int((len - 1) * R)]].
+
+The weak model runs the detect CLI's batches (detect.image_sizes / distributed.size_batches /
+detect._decoded_batches), so its results are that CLI's.  After each weak batch's replay a hook on the
+batch's stream (models.run_batches post=) runs csrc/offload.hip: the detector's raw outputs -> the .npy
+rows -> the stage-24 features -> the estimate -> flag = estimate > threshold -> the flagged images'
+decoded bytes packed to the front of a device tensor; flags, estimates and the packed count come back
+with the detections.  A generator feeds the strong model's run_batches from those packed tensors: per
+image size it queues the survivors and, whenever --strong-batch of them wait (or the size group ends),
+gathers them into one device batch.  The strong batches are therefore exactly
+distributed.size_batches(selected images, strong_batch), the offloaded images are neither decoded nor
+uploaded twice, and the device memory held for waiting images is a few batches.
+
+Writes save_dir/<name>.npy for every image (the strong rows where offloaded, the weak rows otherwise;
+fmt.save_npy), save_dir/offload.npz {names, estimate float64, offloaded bool, threshold, ratio_realized}
+and, with --weak-dir, every weak file.  One process, one GPU: sharding the cascade is not built.
+"""
+import argparse
+import ctypes
+import os
+import pickle
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import fmt, ops
+
+
+# ---------------------------------------------------------------------------------------- estimator file
+class Estimator:
+    """A trained reward estimator on `width` stage-24 features: kind "linear" (mean, scale, coef
+    float64 [width], intercept) or "mlp" (dims, state float32 in estimator.MlpSpec's layout)."""
+
+    def __init__(self, kind, width, **data):
+        self.kind, self.width = kind, int(width)
+        self.__dict__.update(data)
+        self._dev = None
+
+    def device_data(self, device):
+        """The model's arrays on the device (uploaded once)."""
+        if self._dev is None or self._dev[0] != torch.device(device):
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            if self.kind == "linear":
+                d = {"mean": t(self.mean), "scale": t(self.scale), "coef": t(self.coef),
+                     "intercept": t(np.array([self.intercept], np.float64))}
+            else:
+                d = {"state": t(self.state)}
+            self._dev = (torch.device(device), d)
+        return self._dev[1]
+
+    def decide(self, feat, threshold, est, flag, scratch, stream=None):
+        """edgedet_offload_decide on feat [B, width] float64 (device): est [B] float64 and flag [B] uint8
+        are written on `stream`; scratch = (x32 [B, width], est32 [B]) float32 for an MLP."""
+        B = int(feat.shape[0])
+        d = self.device_data(feat.device)
+        if self.kind == "linear":
+            args = (ops._ptr(d["mean"]), ops._ptr(d["scale"]), ops._ptr(d["coef"]), ops._ptr(d["intercept"]), 0, None,
+                    None, None, None)
+        else:
+            dims = (ctypes.c_int32 * len(self.dims))(*self.dims)
+            args = (None, None, None, None, len(self.dims) - 1, dims, ops._ptr(d["state"]), ops._ptr(scratch[0]),
+                    ops._ptr(scratch[1]))
+        ops.check(ops.lib().edgedet_offload_decide(ops._ptr(feat), B, self.width, *args, float(threshold),
+                                                   ops._ptr(est), ops._ptr(flag), ops.stream_handle(stream)))
+
+
+def load_estimator(path, width):
+    """The estimator of a wts<fold>.pickle / wts<fold>.pth file; raises ValueError on a KNR file, on a
+    file that is neither, and when the model's feature width is not `width`."""
+    from .estimator import MlpSpec
+    if str(path).endswith(".pth"):
+        named = torch.load(path, map_location="cpu", weights_only=True)
+        named = {k: v.numpy() for k, v in named.items() if torch.is_tensor(v)}
+        L = 0
+        while f"linear_stacks.{L}.0.weight" in named:
+            L += 1
+        if L == 0:
+            raise ValueError(f"{path}: no linear_stacks.<l>.0.weight tensors (not an estimator --model CNN file)")
+        shapes = [tuple(named[f"linear_stacks.{l}.0.weight"].shape) for l in range(L)]
+        dims = [int(shapes[0][1])] + [int(s[0]) for s in shapes]
+        if any(len(s) != 2 for s in shapes) or any(shapes[l][1] != dims[l] for l in range(L)) or dims[-1] != 1:
+            raise ValueError(f"{path}: the linear layers {shapes} do not chain to one output")
+        if dims[0] != width:
+            raise ValueError(f"{path}: the MLP takes {dims[0]} features, the cascade makes {width} "
+                             f"(num_class + 5 k: check --k and --dataset)")
+        spec = MlpSpec(dims)
+        missing = [k for k in spec.unpack(np.zeros(spec.ns, np.float32)) if k not in named]
+        if missing:
+            raise ValueError(f"{path}: missing tensors {missing[:4]}")
+        return Estimator("mlp", width, dims=dims, state=spec.pack(named))
+    with open(path, "rb") as f:
+        m = pickle.load(f)
+    if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
+        raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
+    if m.get("model") == "KNR" or "coef" not in m:
+        raise ValueError(f"{path}: a KNR file holds no training rows, so the cascade cannot predict from it; "
+                         f"train --model LR, EN, BR or CNN")
+    mean, scale, coef = (np.ascontiguousarray(np.asarray(m[k], np.float64).reshape(-1)) for k in ("mean", "scale", "coef"))
+    if not (len(mean) == len(scale) == len(coef) == width):
+        raise ValueError(f"{path}: the model takes {len(coef)} features, the cascade makes {width} "
+                         f"(num_class + 5 k: check --k and --dataset)")
+    return Estimator("linear", width, mean=mean, scale=scale, coef=coef, intercept=float(m["intercept"]))
+
+
+def ratio_threshold(train_est, ratio):
+    """test.py:35."""
+    train_est = np.asarray(train_est)
+    return train_est[np.argsort(-train_est)[int((len(train_est) - 1) * ratio)]]
+
+
+def resolve_threshold(opts):
+    if opts.threshold is not None:
+        return float(opts.threshold)
+    with np.load(os.path.join(opts.estimates, f"estimate{opts.fold}.npz"), allow_pickle=False) as z:
+        return float(ratio_threshold(z["train_est"], opts.ratio))
+
+
+# ---------------------------------------------------------------------------------------- strong queue
+class BatchQueue:
+    """The strong stage's batching as pure logic.  push(size, items) takes the survivors of one weak
+    batch (all of one image size) and returns the batches that became ready; a change of size ends the
+    previous size group and flushes its remainder first; finish() flushes what is left.  Fed the weak
+    batches of distributed.size_batches (equal sizes arrive together), the batches that come out are
+    size_batches(selected images, batch)."""
+
+    def __init__(self, batch):
+        self.batch, self.size, self.items = int(batch), None, []
+        if self.batch < 1:
+            raise ValueError("strong batch must be >= 1")
+
+    def push(self, size, items):
+        out = []
+        if self.size is not None and size != self.size:
+            out += self.finish()
+        self.size = size
+        self.items += list(items)
+        while len(self.items) >= self.batch:
+            out.append((self.size, self.items[:self.batch]))
+            self.items = self.items[self.batch:]
+        return out
+
+    def finish(self):
+        out = [(self.size, self.items)] if self.items else []
+        self.items = []
+        return out
+
+
+# ---------------------------------------------------------------------------------------- device chain
+def format_rows(count, boxes, scores, labels, H, W, dataset="coco", rows=None, nrow=None, stream=None):
+    """edgedet_offload_rows: device tensors count [B] int32, boxes [B,K,4] f32, scores [B,K] f32, labels
+    [B,K] int64 -> (rows [B,K,6] float64, nrow [B] int32); the first nrow[b] rows of image b are
+    fmt.format_batch's."""
+    ops._need_cuda(count, boxes, scores, labels, rows, nrow)
+    B, K = (int(v) for v in scores.shape)
+    if rows is None:
+        rows = torch.zeros((B, K, 6), dtype=torch.float64, device=scores.device)
+        nrow = torch.zeros((B,), dtype=torch.int32, device=scores.device)
+    ops.check(ops.lib().edgedet_offload_rows(ops._ptr(count), ops._ptr(boxes), ops._ptr(scores), ops._ptr(labels), B, K,
+                                             int(H), int(W), int(dataset != "coco"), ops._ptr(rows), ops._ptr(nrow),
+                                             ops.stream_handle(stream)))
+    return rows, nrow
+
+
+def row_features(rows, nrow, num_class, k=25, out=None, stream=None):
+    """edgedet_offload_features: padded rows [B,K,6] float64 + nrow [B] -> [B, num_class + 5 k] float64,
+    features.output_features' bytes."""
+    ops._need_cuda(rows, nrow, out)
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    if out is None:
+        out = torch.empty((B, num_class + 5 * k), dtype=torch.float64, device=rows.device)
+    ops.check(ops.lib().edgedet_offload_features(ops._ptr(rows), ops._ptr(nrow), B, K, int(num_class), int(k),
+                                                 ops._ptr(out), ops.stream_handle(stream)))
+    return out
+
+
+def pack(flag, src, dst, count, index, stream=None):
+    """edgedet_offload_pack: the images of src [B,...] uint8 whose flag [B] uint8 is set, copied to the
+    front of dst in index order; count [1] and index [B] int32 (device)."""
+    ops._need_cuda(flag, src, dst, count, index)
+    B = int(src.shape[0])
+    ops.check(ops.lib().edgedet_offload_pack(ops._ptr(flag), ops._ptr(src), B, src.numel() // B, ops._ptr(dst),
+                                             ops._ptr(count), ops._ptr(index), ops.stream_handle(stream)))
+
+
+def gather(pairs, out=None, stream=None):
+    """edgedet_offload_gather: pairs [(device uint8 tensor [B,3,H,W], image index)] -> one contiguous
+    [len(pairs),3,H,W] uint8 device tensor."""
+    ops._need_cuda(*[t for t, _ in pairs])
+    n, shape = len(pairs), tuple(pairs[0][0].shape[1:])
+    if any(tuple(t.shape[1:]) != shape or t.dtype != torch.uint8 or not 0 <= int(j) < t.shape[0] for t, j in pairs):
+        raise ValueError("gather: uint8 batches of one image shape, indices inside them")
+    if out is None:
+        out = torch.empty((n,) + shape, dtype=torch.uint8, device=pairs[0][0].device)
+    src = (ctypes.c_void_p * n)(*[t.data_ptr() for t, _ in pairs])
+    idx = (ctypes.c_int32 * n)(*[int(j) for _, j in pairs])
+    ops.check(ops.lib().edgedet_offload_gather(src, idx, n, out.numel() // n, ops._ptr(out), ops.stream_handle(stream)))
+    return out
+
+
+class Chain:
+    """The run_batches post hook of the weak model: rows -> features -> estimate -> flags -> pack on the
+    slot's stream.  Its device scratch and pinned result buffers live on the slot; the packed images are
+    a fresh tensor per batch, handed on to the strong stage."""
+
+    def __init__(self, estimator, threshold, num_class, k, dataset):
+        self.est, self.threshold, self.num_class, self.k, self.dataset = estimator, float(threshold), num_class, k, dataset
+
+    def buffers(self, plan, sl):
+        B, K = (int(v) for v in plan.out_score.shape)
+        D = self.num_class + 5 * self.k
+        buf = sl.get("offload")
+        if buf is None or buf["key"] != (B, K, D):
+            dev = plan.device
+            d = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+            p = lambda shape, dt: torch.zeros(shape, dtype=dt, pin_memory=True)  # noqa: E731
+            buf = sl["offload"] = {
+                "key": (B, K, D), "rows": d((B, K, 6), torch.float64), "nrow": d((B,), torch.int32),
+                "feat": d((B, D), torch.float64), "x32": d((B, D), torch.float32), "est32": d((B,), torch.float32),
+                "est": d((B,), torch.float64), "flag": d((B,), torch.uint8), "count": d((1,), torch.int32),
+                "index": d((B,), torch.int32),
+                "h_est": p((B,), torch.float64), "h_flag": p((B,), torch.uint8), "h_count": p((1,), torch.int32),
+                "h_index": p((B,), torch.int32)}
+        return buf
+
+    def __call__(self, plan, sl, stream, tag):
+        if not plan.u8:
+            raise ValueError("the cascade packs the decoded uint8 images: the weak batches must be uint8")
+        b = self.buffers(plan, sl)
+        format_rows(plan.out_count.tensor(), plan.out_box.tensor(), plan.out_score.tensor(), plan.out_label.tensor(),
+                    plan.H, plan.W, self.dataset, b["rows"], b["nrow"], stream)
+        row_features(b["rows"], b["nrow"], self.num_class, self.k, b["feat"], stream)
+        self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"]), stream)
+        images = plan.input.tensor()
+        packed = torch.empty_like(images)  # this batch's own: it outlives the slot's next use
+        pack(b["flag"], images, packed, b["count"], b["index"], stream)
+        for k in ("est", "flag", "count", "index"):
+            b["h_" + k].copy_(b[k], non_blocking=True)
+        sl["post"] = {"estimate": b["h_est"], "flag": b["h_flag"], "count": b["h_count"], "index": b["h_index"],
+                      "packed": packed}
+
+
+# ---------------------------------------------------------------------------------------- the cascade
+def run(img_dir, estimator, threshold, k=25, dataset="coco", weak="ssd", strong="faster_rcnn", weak_path="",
+        strong_path="", weak_batch=0, strong_batch=0, decode="gpu", on_rows=None, device="cuda:0"):
+    """Run the cascade on a directory of images.  estimator: an Estimator or a wts file; weak / strong:
+    a detect CLI model name (loaded from weak_path / strong_path) or a detector of models.py.  Returns
+    {names, estimate [n] float64, offloaded [n] bool, threshold, ratio_realized, rows {name: final
+    rows}, weak_rows {name: weak rows}, strong_batches [[name, ...], ...], seconds {phase: host
+    seconds}}.  on_rows(kind, name, rows)
+    is called as rows become ready (kind "weak" for every image, "final" once per image)."""
+    import time
+    from . import detect, distributed as dist_mod
+    clock = {"start": time.perf_counter(), "strong_model": 0.0}
+    if not torch.cuda.is_available():
+        raise RuntimeError("edgeml_amd.offload needs an MI355X (HIP) device; there is no CPU path")
+    num_class = 20 if dataset == "voc" else 80      # classes of the .npy rows (features.main)
+    det_classes = 91 if dataset == "coco" else 21   # classes of the detectors (detect.main)
+    if not isinstance(estimator, Estimator):
+        estimator = load_estimator(estimator, num_class + 5 * k)
+    if estimator.width != num_class + 5 * k:
+        raise ValueError(f"the estimator takes {estimator.width} features, the cascade makes {num_class + 5 * k}")
+    torch.cuda.set_device(device)
+    data = detect.ObjectDetectionDataset(img_dir)
+    names = data.img_names
+    load = lambda m, path: m if not isinstance(m, str) else \
+        detect.load_weak_models(m, path, det_classes).to(device).eval()  # noqa: E731
+    weak_model = load(weak, weak_path)
+    clock["weak_model"] = time.perf_counter()
+    sizes = detect.image_sizes(data)
+    clock["sizes"] = time.perf_counter()
+    chunks = dist_mod.size_batches(sizes, min(weak_batch or weak_model.max_batch, weak_model.max_batch))
+    tagged = (((nm, hw), buf) for nm, hw, buf in
+              detect._decoded_batches(data, chunks, sizes, device_decode=decode == "gpu"))
+    chain = Chain(estimator, threshold, num_class, k, dataset)
+    est, flags, weak_rows, rows, strong_batches = {}, {}, {}, {}, []
+    tell = on_rows or (lambda kind, name, r: None)
+    strong_model = [None]
+
+    def strong_input():
+        """Drives the weak model; yields the strong model's batches ((names, (H, W)), device tensor)."""
+        queue = None
+
+        def assemble(ready):
+            for (h, w), items in ready:
+                cur = torch.cuda.current_stream()
+                batch = gather([(t, j) for _, t, j in items], stream=cur)
+                for t in {id(t): t for _, t, _ in items}.values():
+                    t.record_stream(cur)  # allocated on the weak slot's stream, read on this one
+                strong_batches.append([n for n, _, _ in items])
+                yield ([n for n, _, _ in items], (h, w)), batch
+
+        for (nm, (h, w)), counts, boxes, scores, labels, ex in weak_model.run_batches(tagged, raw=True, post=chain):
+            for name, r in zip(nm, fmt.format_batch(boxes, scores, labels, counts, h, w, dataset)):
+                weak_rows[name] = r
+                tell("weak", name, r)
+            sel = np.nonzero(ex["flag"][:len(nm)])[0]
+            if int(ex["count"][0]) != len(sel) or not np.array_equal(ex["index"][:len(sel)], sel):
+                raise ops.EdgeDetError("offload: the packed images do not match the flags")
+            for j, name in enumerate(nm):
+                est[name], flags[name] = float(ex["estimate"][j]), bool(ex["flag"][j])
+                if not flags[name]:
+                    rows[name] = weak_rows[name]
+                    tell("final", name, rows[name])
+            if len(sel) == 0:
+                continue
+            if queue is None:
+                if strong_model[0] is None:
+                    t0 = time.perf_counter()
+                    strong_model[0] = load(strong, strong_path)  # only once an image is offloaded
+                    clock["strong_model"] = time.perf_counter() - t0
+                queue = BatchQueue(min(strong_batch or strong_model[0].max_batch, strong_model[0].max_batch))
+            yield from assemble(queue.push((h, w), [(nm[i], ex["packed"], j) for j, i in enumerate(sel)]))
+        if queue is not None:
+            yield from assemble(queue.finish())
+
+    feed = strong_input()
+    first = next(feed, None)  # runs the weak model up to the first strong batch (all of it when there is none)
+    if first is not None:
+        import itertools
+        for (nm, (h, w)), counts, boxes, scores, labels in strong_model[0].run_batches(
+                itertools.chain([first], feed), raw=True):
+            for name, r in zip(nm, fmt.format_batch(boxes, scores, labels, counts, h, w, dataset)):
+                rows[name] = r
+                tell("final", name, r)
+    offloaded = np.array([flags[n] for n in names], dtype=bool)
+    end = time.perf_counter()
+    # host seconds per phase (EDGEDET_DETECT_TIMING=1: the CLI prints them, as the detect CLI does)
+    seconds = {"weak_model": clock["weak_model"] - clock["start"], "sizes": clock["sizes"] - clock["weak_model"],
+               "strong_model": clock["strong_model"], "engine": end - clock["sizes"] - clock["strong_model"]}
+    return {"seconds": seconds, "names": list(names), "estimate": np.array([est[n] for n in names], dtype=np.float64),
+            "offloaded": offloaded, "threshold": float(threshold),
+            "ratio_realized": float(offloaded.mean()) if len(names) else 0.0,
+            "rows": rows, "weak_rows": weak_rows, "strong_batches": strong_batches}
+
+
+def main(opts):
+    import concurrent.futures as cf
+    from .distributed import usable_cpus
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("edgeml_amd.offload runs in one process on one GPU: sharding the cascade over several "
+                         "GPUs is not built (run it without torchrun)")
+    num_class = 20 if opts.dataset == "voc" else 80
+    try:
+        estimator = load_estimator(opts.estimator, num_class + 5 * opts.k)  # before any image is read
+    except ValueError as e:
+        raise SystemExit(f"edgeml_amd.offload: {e}") from None
+    threshold = resolve_threshold(opts)
+    Path(opts.save_dir).mkdir(parents=True, exist_ok=True)
+    if opts.weak_dir:
+        Path(opts.weak_dir).mkdir(parents=True, exist_ok=True)
+    with cf.ThreadPoolExecutor(usable_cpus()) as writers:
+        pending = []
+
+        def on_rows(kind, name, r):
+            if kind == "final":
+                pending.append(writers.submit(fmt.save_npy, opts.save_dir, name, r))
+            elif opts.weak_dir:
+                pending.append(writers.submit(fmt.save_npy, opts.weak_dir, name, r))
+
+        res = run(opts.img_dir, estimator, threshold, opts.k, opts.dataset, opts.weak, opts.strong, opts.weak_path,
+                  opts.strong_path, opts.weak_batch, opts.strong_batch, opts.decode, on_rows)
+        for f in pending:
+            f.result()  # re-raise a failed write
+    np.savez(os.path.join(opts.save_dir, "offload.npz"), names=np.array(res["names"], dtype=str),
+             estimate=res["estimate"], offloaded=res["offloaded"], threshold=np.float64(res["threshold"]),
+             ratio_realized=np.float64(res["ratio_realized"]))
+    if os.environ.get("EDGEDET_DETECT_TIMING") == "1":
+        print("offload timing (s): " + ", ".join(f"{k} {v:.3f}" for k, v in res["seconds"].items()) +
+              f", images {len(res['names'])}", file=sys.stderr, flush=True)
+    print(f"offloaded {int(res['offloaded'].sum())} of {len(res['names'])} images "
+          f"(threshold {res['threshold']!r}, realised ratio {res['ratio_realized']:.4f})")
+    return res
+
+
+def getargs(argv=None):
+    a = argparse.ArgumentParser(prog="edgeml_amd.offload")
+    a.add_argument("img_dir", help="Directory of the images to run the cascade on.")
+    a.add_argument("save_dir", help="Directory for the detections (<name>.npy) and offload.npz.")
+    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR) or wts<fold>.pth (CNN).")
+    a.add_argument("--ratio", type=float, default=None, help="Offloading ratio: the threshold is test.py:35's on --estimates.")
+    a.add_argument("--estimates", type=str, default=None, help="Directory holding estimate<fold>.npz (with --ratio).")
+    a.add_argument("--threshold", type=float, default=None, help="Offload an image when its estimate exceeds this.")
+    a.add_argument("--fold", type=int, default=1)
+    a.add_argument("--k", type=int, default=25, help="Top-K bounding boxes of the stage-24 features.")
+    a.add_argument("--dataset", choices=("coco", "voc"), default="coco")
+    a.add_argument("--weak", type=str, default="ssd")
+    a.add_argument("--strong", type=str, default="faster_rcnn")
+    a.add_argument("--weak-path", type=str, default="")
+    a.add_argument("--strong-path", type=str, default="")
+    a.add_argument("--weak-dir", type=str, default="", help="Also write every weak detection file here.")
+    a.add_argument("--weak-batch", type=int, default=0, help="Images per weak engine call (0 = model default).")
+    a.add_argument("--strong-batch", type=int, default=0, help="Images per strong engine call (0 = model default).")
+    a.add_argument("--decode", choices=("gpu", "host"), default="gpu")
+    opts = a.parse_args(argv)
+    if (opts.threshold is None) == (opts.ratio is None):
+        a.error("give either --threshold T or --ratio R with --estimates EST_DIR")
+    if opts.ratio is not None and (opts.estimates is None or not 0.0 <= opts.ratio <= 1.0):
+        a.error("--ratio R (0..1) needs --estimates EST_DIR")
+    if opts.threshold is not None and opts.estimates is not None:
+        a.error("--estimates goes with --ratio, not with --threshold")
+    return opts
+
+
+if __name__ == "__main__":
+    main(getargs())
+    sys.exit(0)

@@ -58,6 +58,8 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_reg_workspace_size", "edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh",
            "edgedet_reg_fit_lr", "edgedet_reg_fit_en", "edgedet_reg_fit_br", "edgedet_reg_predict",
            "edgedet_knn_fit_predict",
+           "edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide", "edgedet_offload_pack",
+           "edgedet_offload_gather",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
            "edgedet_model_prepare_host", "edgedet_model_forward", "edgedet_model_max_detections",
            "edgedet_model_records", "edgedet_ssdlite_workspace_size", "edgedet_ssdlite_forward",
@@ -156,6 +158,15 @@ def lib():
                                           _vp, _vp]
     for name in ("edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh", "edgedet_reg_fit_lr",
                  "edgedet_reg_fit_br", "edgedet_reg_fit_en", "edgedet_reg_predict", "edgedet_knn_fit_predict"):
+        getattr(L, name).restype = ctypes.c_int
+    L.edgedet_offload_rows.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
+    L.edgedet_offload_features.argtypes = [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]
+    L.edgedet_offload_decide.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _dbl, _vp, _vp,
+                                         _vp]
+    L.edgedet_offload_pack.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]
+    L.edgedet_offload_gather.argtypes = [_vp, _vp, _i32, _i64, _vp, _vp]
+    for name in ("edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide",
+                 "edgedet_offload_pack", "edgedet_offload_gather"):
         getattr(L, name).restype = ctypes.c_int
     _u64 = ctypes.c_uint64
     L.edgedet_model_weights_size.argtypes = [_i32, _i32, _i32]

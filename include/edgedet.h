@@ -475,6 +475,48 @@ int edgedet_knn_fit_predict(const double* x, int64_t N, int64_t D, const double*
                             const double* scale, int32_t k, void* ws, int64_t ws_bytes, double* est, int32_t* nbr,
                             void* stream);
 
+/* ------------------------------------------------------------------ offloading cascade (csrc/offload.hip) */
+/*
+ * The on-device decision chain between the weak and the strong detector (edgeml_amd.offload); every
+ * call is asynchronous on `stream` and the caller owns every buffer.
+ *
+ * edgedet_offload_rows: detect.py:79-105 on a plan's raw outputs count [B], boxes [B][K][4], scores
+ * [B][K], labels [B][K] of H x W images: rows [B][K][6] float64 [cls, xc, yc, w, h, conf], each image's
+ * kept rows (coco: the COCO-91 -> YOLO-80 map without the 11 dropped ids, an id outside 0..90 dropped
+ * too; voc != 0: label - 1, label 0 dropped) compacted to the front in score order, nrow [B] their
+ * count.  The first nrow rows are byte-identical to numpy's float32 arithmetic promoted to float64; the
+ * rows past them are not written.
+ */
+int edgedet_offload_rows(const int32_t* count, const float* boxes, const float* scores, const int64_t* labels,
+                         int64_t B, int64_t K, int32_t H, int32_t W, int32_t voc, double* rows, int32_t* nrow,
+                         void* stream);
+/* edgedet_output_features on padded rows [B][K][6] with nrow [B] kept rows each: out [B][num_class + 5 k],
+ * byte-identical to it (counts over the first min(nrow, k) rows, int(cls) truncated, zeros beyond). */
+int edgedet_offload_features(const double* rows, const int32_t* nrow, int64_t B, int64_t K, int32_t num_class,
+                             int32_t k, double* out, void* stream);
+/*
+ * est [B] = the estimator on feat [B][D], flag [B] = est > threshold (strict, test.py:37).  L = 0: a
+ * linear model, est by edgedet_reg_predict (folds = 1; mean, scale, coef [D] and intercept [1] on the
+ * device).  L >= 1: an MLP of L linear layers (dims on the host, state on the device, as
+ * edgedet_mlp_predict takes them): feat is cast to float32 into x32 [B][D], est32 [B] comes from
+ * edgedet_mlp_predict and est is its promotion to float64.  The estimates are those two exports' bit for
+ * bit: their kernels run unchanged.
+ */
+int edgedet_offload_decide(const double* feat, int64_t B, int64_t D, const double* mean, const double* scale,
+                           const double* coef, const double* intercept, int32_t L, const int32_t* dims,
+                           const float* state, float* x32, float* est32, double threshold, double* est,
+                           uint8_t* flag, void* stream);
+/* The images b of src [B][image_bytes] with flag[b] != 0 copied to the front of dst in index order
+ * (flags read on the device); *count their number, index[0 .. count) their source indices.  16-byte
+ * copies where an image's two ends are 16-byte aligned, bytes otherwise and for the tail.  Nothing is
+ * written past the count-th image or index. */
+int edgedet_offload_pack(const uint8_t* flag, const uint8_t* src, int64_t B, int64_t image_bytes, uint8_t* dst,
+                         int32_t* count, int32_t* index, void* stream);
+/* dst [n_images][image_bytes]: image j is image index[j] of the device batch src[j] (1 <= n_images <= 64;
+ * src and index are host arrays, passed to the kernel by value). */
+int edgedet_offload_gather(const void* const* src, const int32_t* index, int32_t n_images, int64_t image_bytes,
+                           uint8_t* dst, void* stream);
+
 /* ------------------------------------------------------------------ image ingest (read_image) */
 /*
  * torchvision.io.read_image(path, ImageReadMode.RGB) of detect.py:55-58 for baseline JPEGs, split
