@@ -28,9 +28,10 @@ stream (tests/test_gpu_estimator.py).
 --model LR | EN | BR | KNR runs regression.py's LinearRegression, ElasticNet, BayesianRidge and
 KNeighborsRegressor (behind fit_model's StandardScaler, float64) through edgeml_amd.regress
 (csrc/regress.hip): estimate<k>.npz goes to <save_dir> itself (regression.py:447-448) and,
-with --model-dir, wts<k>.pickle holds plain numpy data instead of sklearn objects.  SGD, RFR, GBR (random
-streams), SVR, LSVR (libsvm / liblinear dual solvers) and the hidden-layer feature maps of the external
-YOLOv5 (stages 0-23) are out of scope; the CLI exits naming what is built.
+with --model-dir, wts<k>.pickle holds plain numpy data instead of sklearn objects.  SVR and LSVR have a
+module and CLI of their own, edgeml_amd.svr.  SGD, RFR, GBR (random streams) and the
+hidden-layer feature maps of the external YOLOv5 (stages 0-23) are out of scope; this CLI
+exits naming what it builds.
 """
 import argparse
 import ctypes
@@ -244,8 +245,9 @@ def check_model(opts):
     if opts.model != "CNN" and opts.model not in REGRESSORS:
         why = ("SGD, RFR and GBR draw random streams that cannot be reproduced, SVR and LSVR need the libsvm / "
                "liblinear dual solvers" if opts.model in NOT_BUILT else f"'{opts.model}' is no model of regression.py")
+        also = ".  python -m edgeml_amd.svr fits SVR and LSVR" if opts.model in ("SVR", "LSVR") else ""
         raise SystemExit(f"edgeml_amd.estimator builds {built} on the stage-24 output features; {why}: "
-                         f"--model {opts.model} is not built")
+                         f"--model {opts.model} is not built{also}")
 
 
 def fold_targets(reward, split, normalize, dtype):

@@ -80,8 +80,9 @@ class Estimator:
 
 
 def load_estimator(path, width):
-    """The estimator of a wts<fold>.pickle / wts<fold>.pth file; raises ValueError on a KNR file, on a
-    file that is neither, and when the model's feature width is not `width`."""
+    """The estimator of a wts<fold>.pickle / wts<fold>.pth file (an LSVR file of edgeml_amd.svr is a linear
+    model); raises ValueError on a KNR file, on an SVR file, on a file that is neither, and when the
+    model's feature width is not `width`."""
     from .estimator import MlpSpec
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
@@ -107,6 +108,9 @@ def load_estimator(path, width):
         m = pickle.load(f)
     if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
         raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
+    if m.get("model") == "SVR":
+        raise ValueError(f"{path}: an SVR file holds support vectors, and the cascade does not predict from them "
+                         f"yet; train --model LSVR, LR, EN, BR or CNN")
     if m.get("model") == "KNR" or "coef" not in m:
         raise ValueError(f"{path}: a KNR file holds no training rows, so the cascade cannot predict from it; "
                          f"train --model LR, EN, BR or CNN")

@@ -58,6 +58,8 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_reg_workspace_size", "edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh",
            "edgedet_reg_fit_lr", "edgedet_reg_fit_en", "edgedet_reg_fit_br", "edgedet_reg_predict",
            "edgedet_knn_fit_predict",
+           "edgedet_svr_workspace_size", "edgedet_svr_kernel_matrix", "edgedet_svr_fit", "edgedet_svr_predict",
+           "edgedet_lsvr_fit",
            "edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide", "edgedet_offload_pack",
            "edgedet_offload_gather",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
@@ -158,6 +160,16 @@ def lib():
                                           _vp, _vp]
     for name in ("edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh", "edgedet_reg_fit_lr",
                  "edgedet_reg_fit_br", "edgedet_reg_fit_en", "edgedet_reg_predict", "edgedet_knn_fit_predict"):
+        getattr(L, name).restype = ctypes.c_int
+    L.edgedet_svr_workspace_size.argtypes = [_vp, _i32, _i64, _i32]
+    L.edgedet_svr_workspace_size.restype = _i64
+    L.edgedet_svr_kernel_matrix.argtypes = [_vp, _i64, _i64, _dbl, _vp, _vp, _vp, _vp]
+    L.edgedet_svr_fit.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _dbl, _i32, _vp,
+                                  _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_svr_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_lsvr_fit.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _i32,
+                                   _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
+    for name in ("edgedet_svr_kernel_matrix", "edgedet_svr_fit", "edgedet_svr_predict", "edgedet_lsvr_fit"):
         getattr(L, name).restype = ctypes.c_int
     L.edgedet_offload_rows.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
     L.edgedet_offload_features.argtypes = [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]

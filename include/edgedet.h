@@ -475,6 +475,52 @@ int edgedet_knn_fit_predict(const double* x, int64_t N, int64_t D, const double*
                             const double* scale, int32_t k, void* ws, int64_t ws_bytes, double* est, int32_t* nbr,
                             void* stream);
 
+/* ------------------------------------------------------------------ support vector regressors (regression.py) */
+/*
+ * regression.py's SVR(kernel='rbf', C, epsilon) and LinearSVR(C, epsilon) behind fit_model's StandardScaler,
+ * float64, every cross-validation fold in flight, each solved to the optimum of its strongly convex
+ * objective (csrc/svr.hip).  x, y, tr_idx, tr_off_host, tr_off, folds, mean and scale are the
+ * estimator regressors' (tr_idx is required; every fold non-empty; mean and scale from edgedet_reg_scaler).
+ * With T = tr_off[F] the workspace holds Z [T][D], the standardised training rows of every fold, their
+ * squared norms [T] and, for SVR, every fold's kernel matrix [n_f][n_f]; it is 8-byte aligned.
+ *
+ * edgedet_svr_workspace_size: its bytes (with_kernel != 0: for edgedet_svr_fit); < 0 on bad sizes.
+ */
+int64_t edgedet_svr_workspace_size(const int64_t* tr_off_host, int32_t folds, int64_t D, int32_t with_kernel);
+/* The RBF kernel matrix of one matrix z [n][D], taken as it is: K [n][n] = exp(-gamma max(|a|^2 + |b|^2 -
+ * 2 a.b, 0)) with the dot products by the fp64 matrix instruction; norm [n] receives |z_i|^2, gamma [1] the
+ * value used: gamma_in when > 0, otherwise sklearn's gamma='scale', 1 / (D var), var the population variance
+ * of all entries of z (1 when var is 0). */
+int edgedet_svr_kernel_matrix(const double* z, int64_t n, int64_t D, double gamma_in, double* norm, double* gamma,
+                              double* K, void* stream);
+/* SVR: SMO on beta = alpha - alpha*, minimising 1/2 beta^T K beta - y^T beta + epsilon |beta|_1 on -C <= beta
+ * <= C, sum beta = 0, with libsvm's second-order working-set selection, until libsvm's maximal KKT violation
+ * m(beta) - M(beta) <= tol holds on a gradient recomputed from beta.  At most 4,000 training rows per fold.
+ * beta [T] (fold f at tr_off[f]), intercept [F] (libsvm's rule), gamma [F] (gamma='scale'), viol [F] the final
+ * violation, iters [F], status [F]: 0 ok, 1 not converged in max_iter.  The workspace keeps Z and the norms
+ * for edgedet_svr_predict. */
+int edgedet_svr_fit(const double* x, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
+                    const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, const double* mean,
+                    const double* scale, double C, double epsilon, double tol, int32_t max_iter, void* ws,
+                    int64_t ws_bytes, double* beta, double* intercept, double* gamma, double* viol, int32_t* iters,
+                    int32_t* status, void* stream);
+/* out [F][N] = sum_j beta_j exp(-gamma_f |z - z_j|^2) + intercept_f for every row of x under every fold's
+ * model, on the workspace edgedet_svr_fit filled: distance tiles, exponential and row sum in one kernel. */
+int edgedet_svr_predict(const double* x, int64_t N, int64_t D, const double* mean, const double* scale,
+                        const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, const void* ws,
+                        int64_t ws_bytes, const double* beta, const double* intercept, const double* gamma,
+                        double* out, void* stream);
+/* LinearSVR (epsilon-insensitive loss, the bias a regularised feature of value 1): exact dual coordinate
+ * descent in natural cyclic order, sixteen coordinates per block, until the duality gap P(X~^T beta) -
+ * D(beta) <= tol, tol = tol_abs when > 0, otherwise tol_rel P(0).  beta [T], v [F][D + 1] = X~^T beta
+ * recomputed from the final beta (coef = v[:D], intercept = v[D]: edgedet_reg_predict predicts), res [F][2] =
+ * {gap, tol}, sweeps [F], status [F]: 0 ok, 1 not converged in max_sweeps. */
+int edgedet_lsvr_fit(const double* x, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
+                     const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, const double* mean,
+                     const double* scale, double C, double epsilon, double tol_abs, double tol_rel,
+                     int32_t max_sweeps, void* ws, int64_t ws_bytes, double* beta, double* v, double* res,
+                     int32_t* sweeps, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ offloading cascade (csrc/offload.hip) */
 /*
  * The on-device decision chain between the weak and the strong detector (edgeml_amd.offload); every
