@@ -9,6 +9,8 @@
 //   edgedet_offload_decide  the estimate of every image by the existing predict kernels
 //                           (edgedet_reg_predict, or edgedet_mlp_predict on the float32 cast of the
 //                           features), then flag = estimate > threshold (test.py:37);
+//   edgedet_offload_flag    that flag alone, for estimates another call wrote (csrc/kpredict.hip's SVR and
+//                           KNR predictions): the same kernel;
 //   offload_pack_kernel     the flagged images of a uint8 batch copied to the front of a destination
 //                           batch in index order (flags read on the device), with their count and
 //                           source indices;
@@ -205,6 +207,16 @@ extern "C" int edgedet_offload_decide(const double* feat, int64_t B, int64_t D, 
     }
     hipLaunchKernelGGL(offload_flag_kernel, dim3((unsigned)cdiv(B, OFFLOAD_NT)), dim3(OFFLOAD_NT), 0,
                        (hipStream_t)stream, L == 0 ? nullptr : est32, est, B, threshold, flag);
+    EDGEDET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int edgedet_offload_flag(const double* est, int64_t B, double threshold, uint8_t* flag, void* stream) {
+    EDGEDET_REQUIRE(est && flag, "offload_flag: null pointer");
+    EDGEDET_REQUIRE(B >= 1 && B <= (int64_t)65535 * OFFLOAD_NT, "offload_flag: bad sizes");
+    // est32 null: the kernel only reads est
+    hipLaunchKernelGGL(offload_flag_kernel, dim3((unsigned)cdiv(B, OFFLOAD_NT)), dim3(OFFLOAD_NT), 0,
+                       (hipStream_t)stream, (const float*)nullptr, const_cast<double*>(est), B, threshold, flag);
     EDGEDET_LAUNCH_CHECK();
     return 0;
 }

@@ -285,7 +285,8 @@ def main_regressor(opts, features, reward, split):
         if opts.model_dir != "":
             Path(opts.model_dir).mkdir(parents=True, exist_ok=True)
             with open(os.path.join(opts.model_dir, f"wts{cv_idx + 1}.pickle"), "wb") as f:
-                pickle.dump(regress.model_data(opts.model, info, cv_idx), f)
+                rows = (features, y) if opts.model == "KNR" else ()  # a KNR model is its training set
+                pickle.dump(regress.model_data(opts.model, info, cv_idx, *rows), f)
     return results, info
 
 

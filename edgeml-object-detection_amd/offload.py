@@ -7,11 +7,14 @@ threshold (the policy test.py:30-42 simulates on saved files, run for real in on
            [--weak-path P] [--strong-path P] [--weak-dir DIR] [--weak-batch N] [--strong-batch N]
            [--decode gpu|host]
 
-WTS is a trained estimator: wts<fold>.pickle as `edgeml_amd.estimator --model LR|EN|BR --model-dir` writes
-it (plain numpy mean, scale, coef, intercept), or wts<fold>.pth as `--model CNN --model-dir` writes it (the
-MLP's tensors under EdgeDetectionNet's state-dict names; the layer widths are read from the weight
-shapes).  A KNR file is refused: it holds no training rows.  The threshold is --threshold, or test.py:35
-on EST_DIR/estimate<fold>.npz: train_est[argsort(-train_est)[int((len - 1) * R)]].
+WTS is a trained estimator: wts<fold>.pickle as `edgeml_amd.estimator --model LR|EN|BR --model-dir` or
+`edgeml_amd.svr --model LSVR --model-dir` writes it (plain numpy mean, scale, coef, intercept), wts<fold>.pth
+as `--model CNN --model-dir` writes it (the MLP's tensors under EdgeDetectionNet's state-dict names; the
+layer widths are read from the weight shapes), or the wts<fold>.pickle of `edgeml_amd.svr --model SVR` (the
+support vectors and their dual coefficients) or of `edgeml_amd.estimator --model KNR` (the fold's training
+rows and targets): those two predict from their stored rows through edgeml_amd.kpredict
+(csrc/kpredict.hip).  A KNR file written before the training rows were stored is refused.  The threshold is
+--threshold, or test.py:35 on EST_DIR/estimate<fold>.npz: train_est[argsort(-train_est)[int((len - 1) * R)]].
 
 The weak model runs the detect CLI's batches (detect.image_sizes / distributed.size_batches /
 detect._decoded_batches), so its results are that CLI's.  After each weak batch's replay a hook on the
@@ -44,7 +47,8 @@ from . import fmt, ops
 # ---------------------------------------------------------------------------------------- estimator file
 class Estimator:
     """A trained reward estimator on `width` stage-24 features: kind "linear" (mean, scale, coef
-    float64 [width], intercept) or "mlp" (dims, state float32 in estimator.MlpSpec's layout)."""
+    float64 [width], intercept), "mlp" (dims, state float32 in estimator.MlpSpec's layout), or "svr" /
+    "knr" (model: the kpredict.KernelModel that predicts from the file's stored rows)."""
 
     def __init__(self, kind, width, **data):
         self.kind, self.width = kind, int(width)
@@ -55,7 +59,9 @@ class Estimator:
         """The model's arrays on the device (uploaded once)."""
         if self._dev is None or self._dev[0] != torch.device(device):
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-            if self.kind == "linear":
+            if self.kind in ("svr", "knr"):
+                d = {"model": self.model.to(device)}  # uploads and standardises the stored rows once
+            elif self.kind == "linear":
                 d = {"mean": t(self.mean), "scale": t(self.scale), "coef": t(self.coef),
                      "intercept": t(np.array([self.intercept], np.float64))}
             else:
@@ -63,11 +69,25 @@ class Estimator:
             self._dev = (torch.device(device), d)
         return self._dev[1]
 
+    def workspace_bytes(self, B):
+        """Bytes of the per-batch workspace an SVR or KNR model needs (edgedet_kmodel_workspace_size); 0 for
+        the other kinds."""
+        return self.model.workspace_bytes(B) if self.kind in ("svr", "knr") else 0
+
     def decide(self, feat, threshold, est, flag, scratch, stream=None):
         """edgedet_offload_decide on feat [B, width] float64 (device): est [B] float64 and flag [B] uint8
-        are written on `stream`; scratch = (x32 [B, width], est32 [B]) float32 for an MLP."""
+        are written on `stream`; scratch = (x32 [B, width], est32 [B]) float32 for an MLP.  An SVR or KNR
+        model takes a third entry, its uint8 workspace (workspace_bytes(B)): its estimates are
+        kpredict.KernelModel's, then edgedet_offload_flag."""
         B = int(feat.shape[0])
         d = self.device_data(feat.device)
+        if self.kind in ("svr", "knr"):
+            if len(scratch) < 3 or scratch[2] is None:
+                raise ValueError(f"the {self.kind} estimator needs its workspace as scratch[2]")
+            d["model"].predict_into(feat, est, scratch[2], stream=stream)
+            ops.check(ops.lib().edgedet_offload_flag(ops._ptr(est), B, float(threshold), ops._ptr(flag),
+                                                     ops.stream_handle(stream)))
+            return
         if self.kind == "linear":
             args = (ops._ptr(d["mean"]), ops._ptr(d["scale"]), ops._ptr(d["coef"]), ops._ptr(d["intercept"]), 0, None,
                     None, None, None)
@@ -79,10 +99,13 @@ class Estimator:
                                                    ops._ptr(est), ops._ptr(flag), ops.stream_handle(stream)))
 
 
-def load_estimator(path, width):
+def load_estimator(path, width, support=False):
     """The estimator of a wts<fold>.pickle / wts<fold>.pth file (an LSVR file of edgeml_amd.svr is a linear
-    model); raises ValueError on a KNR file, on an SVR file, on a file that is neither, and when the
-    model's feature width is not `width`."""
+    model).  A KNR file that holds its training rows ('train', 'target') loads as kind "knr"; with
+    support=True (what the cascade passes) an SVR file loads as kind "svr", otherwise it is refused as before.
+    Raises ValueError on a KNR file without training rows, on a file that is none of these, on inconsistent
+    shapes, and when the model's feature width is not `width`."""
+    from . import kpredict
     from .estimator import MlpSpec
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
@@ -108,9 +131,15 @@ def load_estimator(path, width):
         m = pickle.load(f)
     if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
         raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
-    if m.get("model") == "SVR":
+    if m.get("model") == "SVR" and not support:
         raise ValueError(f"{path}: an SVR file holds support vectors, and the cascade does not predict from them "
                          f"yet; train --model LSVR, LR, EN, BR or CNN")
+    if m.get("model") == "SVR" or (m.get("model") == "KNR" and "train" in m and "target" in m):
+        model = kpredict.load(m)
+        if model.width != width:
+            raise ValueError(f"{path}: the model takes {model.width} features, the cascade makes {width} "
+                             f"(num_class + 5 k: check --k and --dataset)")
+        return Estimator(model.kind, width, model=model)
     if m.get("model") == "KNR" or "coef" not in m:
         raise ValueError(f"{path}: a KNR file holds no training rows, so the cascade cannot predict from it; "
                          f"train --model LR, EN, BR or CNN")
@@ -228,12 +257,14 @@ class Chain:
         B, K = (int(v) for v in plan.out_score.shape)
         D = self.num_class + 5 * self.k
         buf = sl.get("offload")
-        if buf is None or buf["key"] != (B, K, D):
+        wb = self.est.workspace_bytes(B)  # an SVR / KNR model's tiles; 0 otherwise
+        if buf is None or buf["key"] != (B, K, D, wb):
             dev = plan.device
             d = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
             p = lambda shape, dt: torch.zeros(shape, dtype=dt, pin_memory=True)  # noqa: E731
             buf = sl["offload"] = {
-                "key": (B, K, D), "rows": d((B, K, 6), torch.float64), "nrow": d((B,), torch.int32),
+                "key": (B, K, D, wb), "kws": d((wb,), torch.uint8) if wb else None,
+                "rows": d((B, K, 6), torch.float64), "nrow": d((B,), torch.int32),
                 "feat": d((B, D), torch.float64), "x32": d((B, D), torch.float32), "est32": d((B,), torch.float32),
                 "est": d((B,), torch.float64), "flag": d((B,), torch.uint8), "count": d((1,), torch.int32),
                 "index": d((B,), torch.int32),
@@ -248,7 +279,7 @@ class Chain:
         format_rows(plan.out_count.tensor(), plan.out_box.tensor(), plan.out_score.tensor(), plan.out_label.tensor(),
                     plan.H, plan.W, self.dataset, b["rows"], b["nrow"], stream)
         row_features(b["rows"], b["nrow"], self.num_class, self.k, b["feat"], stream)
-        self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"]), stream)
+        self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"], b["kws"]), stream)
         images = plan.input.tensor()
         packed = torch.empty_like(images)  # this batch's own: it outlives the slot's next use
         pack(b["flag"], images, packed, b["count"], b["index"], stream)
@@ -275,7 +306,7 @@ def run(img_dir, estimator, threshold, k=25, dataset="coco", weak="ssd", strong=
     num_class = 20 if dataset == "voc" else 80      # classes of the .npy rows (features.main)
     det_classes = 91 if dataset == "coco" else 21   # classes of the detectors (detect.main)
     if not isinstance(estimator, Estimator):
-        estimator = load_estimator(estimator, num_class + 5 * k)
+        estimator = load_estimator(estimator, num_class + 5 * k, support=True)
     if estimator.width != num_class + 5 * k:
         raise ValueError(f"the estimator takes {estimator.width} features, the cascade makes {num_class + 5 * k}")
     torch.cuda.set_device(device)
@@ -360,7 +391,7 @@ def main(opts):
                          "GPUs is not built (run it without torchrun)")
     num_class = 20 if opts.dataset == "voc" else 80
     try:
-        estimator = load_estimator(opts.estimator, num_class + 5 * opts.k)  # before any image is read
+        estimator = load_estimator(opts.estimator, num_class + 5 * opts.k, support=True)  # before any image is read
     except ValueError as e:
         raise SystemExit(f"edgeml_amd.offload: {e}") from None
     threshold = resolve_threshold(opts)
@@ -395,7 +426,7 @@ def getargs(argv=None):
     a = argparse.ArgumentParser(prog="edgeml_amd.offload")
     a.add_argument("img_dir", help="Directory of the images to run the cascade on.")
     a.add_argument("save_dir", help="Directory for the detections (<name>.npy) and offload.npz.")
-    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR) or wts<fold>.pth (CNN).")
+    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR / LSVR / SVR / KNR) or wts<fold>.pth (CNN).")
     a.add_argument("--ratio", type=float, default=None, help="Offloading ratio: the threshold is test.py:35's on --estimates.")
     a.add_argument("--estimates", type=str, default=None, help="Directory holding estimate<fold>.npz (with --ratio).")
     a.add_argument("--threshold", type=float, default=None, help="Offload an image when its estimate exceeds this.")

@@ -61,7 +61,9 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_svr_workspace_size", "edgedet_svr_kernel_matrix", "edgedet_svr_fit", "edgedet_svr_predict",
            "edgedet_lsvr_fit",
            "edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide", "edgedet_offload_pack",
-           "edgedet_offload_gather",
+           "edgedet_offload_gather", "edgedet_offload_flag",
+           "edgedet_kmodel_prepare", "edgedet_kmodel_workspace_size", "edgedet_svr_model_predict",
+           "edgedet_knn_model_predict",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
            "edgedet_model_prepare_host", "edgedet_model_forward", "edgedet_model_max_detections",
            "edgedet_model_records", "edgedet_ssdlite_workspace_size", "edgedet_ssdlite_forward",
@@ -177,8 +179,17 @@ def lib():
                                          _vp]
     L.edgedet_offload_pack.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]
     L.edgedet_offload_gather.argtypes = [_vp, _vp, _i32, _i64, _vp, _vp]
+    L.edgedet_offload_flag.argtypes = [_vp, _i64, _dbl, _vp, _vp]
+    L.edgedet_kmodel_prepare.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_kmodel_workspace_size.argtypes = [_i64, _i64, _i64, _i32]
+    L.edgedet_kmodel_workspace_size.restype = _i64
+    L.edgedet_svr_model_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _vp, _i64, _vp,
+                                            _vp]
+    L.edgedet_knn_model_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp,
+                                            _vp]
     for name in ("edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide",
-                 "edgedet_offload_pack", "edgedet_offload_gather"):
+                 "edgedet_offload_pack", "edgedet_offload_gather", "edgedet_offload_flag", "edgedet_kmodel_prepare",
+                 "edgedet_svr_model_predict", "edgedet_knn_model_predict"):
         getattr(L, name).restype = ctypes.c_int
     _u64 = ctypes.c_uint64
     L.edgedet_model_weights_size.argtypes = [_i32, _i32, _i32]

@@ -12,7 +12,8 @@ features [N, ...] (flattened), rewards [N] or [k, N] (per-fold targets, e.g. nor
 training set), split (k, N) bool, True = validation.  results: per fold {train_est, val_est (float64),
 train_time, val_time}; info: coef, intercept, mean, scale [k, D] for the linear models, plus per model
 rank / min_ratio (LR), znorm / tol / sweeps (EN), alpha / lambda / n_iter (BR), neighbors [k, N, n_neighbors]
-(KNR: positions within the fold's training rows).  There is no CPU path.
+(KNR: positions within the fold's training rows) and train_rows (KNR: each fold's training rows as dataset
+indices, the order those positions count in).  There is no CPU path.
 """
 import ctypes
 import time
@@ -253,7 +254,7 @@ def fit_knr(features, rewards, split, opts=None, device="cuda"):
                                         p(fo.mean), p(fo.scale), kn, p(ws), wb, p(est), p(nbr), ops.stream_handle()))
     t_fit = _fit_time(t0)
     info = {"neighbors": nbr.cpu().numpy(), "mean": fo.mean.cpu().numpy(), "scale": fo.scale.cpu().numpy(),
-            "fit_time": t_fit, "n_neighbors": kn}
+            "fit_time": t_fit, "n_neighbors": kn, "train_rows": [a.copy() for a in fo.tr]}
     return fo.results(est.cpu().numpy(), t_fit / (k * N)), info
 
 
@@ -261,11 +262,19 @@ FITS = {"LR": fit_lr, "EN": fit_en, "BR": fit_br, "KNR": fit_knr}
 NAMES = {"LR": "Linear Regression", "EN": "Elastic Net", "BR": "Bayesian Ridge", "KNR": "K Neighbors Regressor"}
 
 
-def model_data(name, info, fold):
-    """What wts{k}.pickle holds for one fold: plain numpy data, not sklearn objects."""
+def model_data(name, info, fold, features=None, targets=None):
+    """What wts{k}.pickle holds for one fold: plain numpy data, not sklearn objects.  A KNR model is its
+    training set: given the dataset's features [N, ...] and the targets the fit took ([N] or [k, N]), the file
+    also holds train (the fold's raw training rows, float64 [n, D], training-list order) and target (their
+    targets [n]), which edgeml_amd.kpredict and the offloading cascade predict from."""
     m = {"model": name, "mean": info["mean"][fold].copy(), "scale": info["scale"][fold].copy()}
     if name == "KNR":
         m["n_neighbors"] = int(info["n_neighbors"])
+        if features is not None and targets is not None:
+            rows = info["train_rows"][fold]
+            x = np.asarray(features, dtype=np.float64).reshape(len(features), -1)
+            y = np.asarray(targets, dtype=np.float64)
+            m.update(train=x[rows].copy(), target=(y if y.ndim == 1 else y[fold])[rows].copy())
         return m
     m.update(coef=info["coef"][fold].copy(), intercept=float(info["intercept"][fold]))
     if name == "LR":

@@ -21,7 +21,8 @@ takes regression.py's arguments (and --tol-rel, LSVR's gap tolerance relative to
 default 1e-10 takes too many sweeps), prints fit_model's MSE line per fold, writes estimate<k>.npz into save_dir and,
 with --model-dir, wts<k>.pickle holding plain numpy data: for LSVR {model, mean, scale, coef, intercept, ...},
 which edgeml_amd.offload loads as a linear model; for SVR {model, mean, scale, gamma, support (raw feature
-rows), beta, intercept}, which the cascade does not predict from yet.
+rows), beta, intercept}, which edgeml_amd.kpredict predicts from (csrc/kpredict.hip) and the cascade loads as
+kind "svr".
 """
 import argparse
 import os

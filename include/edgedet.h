@@ -521,6 +521,40 @@ int edgedet_lsvr_fit(const double* x, int64_t N, int64_t D, const double* y, con
                      int32_t max_sweeps, void* ws, int64_t ws_bytes, double* beta, double* v, double* res,
                      int32_t* sweeps, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ prediction from saved SVR / KNR models */
+/*
+ * Estimates from the stored rows of a wts<k>.pickle (csrc/kpredict.hip, edgeml_amd.kpredict): an SVR file's
+ * support vectors with their dual coefficients, or a KNR file's training rows with their targets.  Float64,
+ * 1 <= D <= 255, fixed-order sums: the estimate of a feature row depends on the row and the model only, not on
+ * B or on the row's place in feat.  Every function checks its arguments on the host and returns 0 or a
+ * negative error code (edgedet_last_error) before anything is launched; the calls are asynchronous on `stream`.
+ *
+ * edgedet_kmodel_prepare, once per loaded model: z [n][D] = (rows - mean) * (1 / scale) and norm [n] = |z_i|^2
+ * in the order edgedet_svr_fit and edgedet_knn_fit_predict use (sixteen lanes per row), so a KNR model
+ * reproduces its fit bit for bit.  n = 0 is legal (an SVR without support vectors) and launches nothing.
+ *
+ * edgedet_kmodel_workspace_size: bytes of the workspace of a predict call on B rows (kind 0: SVR, one partial
+ * sum per row and tile of sixteen support vectors; kind 1: KNR, the distances [B][n] and, for a call without
+ * nbr, the selected positions); < 0 on bad sizes.  The workspace is 8-byte aligned.
+ */
+int edgedet_kmodel_prepare(const double* rows, int64_t n, int64_t D, const double* mean, const double* scale,
+                           double* z, double* norm, void* stream);
+int64_t edgedet_kmodel_workspace_size(int64_t n, int64_t D, int64_t B, int32_t kind);
+/* est [B] = sum_j beta_j exp(-gamma max(|z_q|^2 + |z_j|^2 - 2 z_q.z_j, 0)) + intercept for the rows of feat
+ * [B][D], standardised in the load: a wave per tile of 16 rows x 16 support vectors over the whole grid (dot
+ * products by the fp64 matrix instruction), a tile's sixteen terms added by a butterfly, then a row's partial
+ * sums added in an order that depends on n alone.  n = 0: est = intercept (z, norm and beta may be null). */
+int edgedet_svr_model_predict(const double* feat, int64_t B, int64_t D, const double* mean, const double* scale,
+                              const double* z, const double* norm, const double* beta, int64_t n, double gamma,
+                              double intercept, void* ws, int64_t ws_bytes, double* est, void* stream);
+/* KNeighborsRegressor(n_neighbors = k).predict on the rows of feat [B][D]: edgedet_knn_fit_predict's distances
+ * (the same chain per pair) and its selection rule (the k smallest keys, ties at the k-th distance to the
+ * lowest position); est [B] the mean of the selected targets summed in position order, nbr [B][k] (or null)
+ * the selected positions ascending.  1 <= k <= n. */
+int edgedet_knn_model_predict(const double* feat, int64_t B, int64_t D, const double* mean, const double* scale,
+                              const double* z, const double* norm, const double* target, int64_t n, int32_t k,
+                              void* ws, int64_t ws_bytes, double* est, int32_t* nbr, void* stream);
+
 /* ------------------------------------------------------------------ offloading cascade (csrc/offload.hip) */
 /*
  * The on-device decision chain between the weak and the strong detector (edgeml_amd.offload); every
@@ -552,6 +586,9 @@ int edgedet_offload_decide(const double* feat, int64_t B, int64_t D, const doubl
                            const double* coef, const double* intercept, int32_t L, const int32_t* dims,
                            const float* state, float* x32, float* est32, double threshold, double* est,
                            uint8_t* flag, void* stream);
+/* flag [B] = est [B] > threshold (strict, float64): edgedet_offload_decide's last step on estimates another
+ * call wrote (edgedet_svr_model_predict, edgedet_knn_model_predict); the same kernel, est is only read. */
+int edgedet_offload_flag(const double* est, int64_t B, double threshold, uint8_t* flag, void* stream);
 /* The images b of src [B][image_bytes] with flag[b] != 0 copied to the front of dst in index order
  * (flags read on the device); *count their number, index[0 .. count) their source indices.  16-byte
  * copies where an image's two ends are 16-byte aligned, bytes otherwise and for the tail.  Nothing is
