@@ -13,7 +13,9 @@ as `--model CNN --model-dir` writes it (the MLP's tensors under EdgeDetectionNet
 layer widths are read from the weight shapes), or the wts<fold>.pickle of `edgeml_amd.svr --model SVR` (the
 support vectors and their dual coefficients) or of `edgeml_amd.estimator --model KNR` (the fold's training
 rows and targets): those two predict from their stored rows through edgeml_amd.kpredict
-(csrc/kpredict.hip).  A KNR file written before the training rows were stored is refused.  The threshold is
+(csrc/kpredict.hip), or the wts<fold>.pickle of `edgeml_amd.gbr --model GBR` (the boosted trees), which predicts
+through edgeml_amd.gbr.GBRModel (csrc/gbr.hip).  A KNR file written before the training rows were stored is
+refused.  The threshold is
 --threshold, or test.py:35 on EST_DIR/estimate<fold>.npz: train_est[argsort(-train_est)[int((len - 1) * R)]].
 
 The weak model runs the detect CLI's batches (detect.image_sizes / distributed.size_batches /
@@ -48,7 +50,8 @@ from . import fmt, ops
 class Estimator:
     """A trained reward estimator on `width` stage-24 features: kind "linear" (mean, scale, coef
     float64 [width], intercept), "mlp" (dims, state float32 in estimator.MlpSpec's layout), or "svr" /
-    "knr" (model: the kpredict.KernelModel that predicts from the file's stored rows)."""
+    "knr" (model: the kpredict.KernelModel that predicts from the file's stored rows), or "gbr" (model: the
+    gbr.GBRModel that walks the file's trees)."""
 
     def __init__(self, kind, width, **data):
         self.kind, self.width = kind, int(width)
@@ -59,8 +62,8 @@ class Estimator:
         """The model's arrays on the device (uploaded once)."""
         if self._dev is None or self._dev[0] != torch.device(device):
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-            if self.kind in ("svr", "knr"):
-                d = {"model": self.model.to(device)}  # uploads and standardises the stored rows once
+            if self.kind in ("svr", "knr", "gbr"):
+                d = {"model": self.model.to(device)}  # uploads (and standardises the stored rows) once
             elif self.kind == "linear":
                 d = {"mean": t(self.mean), "scale": t(self.scale), "coef": t(self.coef),
                      "intercept": t(np.array([self.intercept], np.float64))}
@@ -81,6 +84,11 @@ class Estimator:
         kpredict.KernelModel's, then edgedet_offload_flag."""
         B = int(feat.shape[0])
         d = self.device_data(feat.device)
+        if self.kind == "gbr":  # edgedet_gbr_model_predict needs no workspace
+            d["model"].predict_into(feat, est, stream=stream)
+            ops.check(ops.lib().edgedet_offload_flag(ops._ptr(est), B, float(threshold), ops._ptr(flag),
+                                                     ops.stream_handle(stream)))
+            return
         if self.kind in ("svr", "knr"):
             if len(scratch) < 3 or scratch[2] is None:
                 raise ValueError(f"the {self.kind} estimator needs its workspace as scratch[2]")
@@ -102,10 +110,11 @@ class Estimator:
 def load_estimator(path, width, support=False):
     """The estimator of a wts<fold>.pickle / wts<fold>.pth file (an LSVR file of edgeml_amd.svr is a linear
     model).  A KNR file that holds its training rows ('train', 'target') loads as kind "knr"; with
-    support=True (what the cascade passes) an SVR file loads as kind "svr", otherwise it is refused as before.
+    support=True (what the cascade passes) an SVR file loads as kind "svr", otherwise it is refused as before;
+    a GBR file of edgeml_amd.gbr loads as kind "gbr".
     Raises ValueError on a KNR file without training rows, on a file that is none of these, on inconsistent
     shapes, and when the model's feature width is not `width`."""
-    from . import kpredict
+    from . import gbr, kpredict
     from .estimator import MlpSpec
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
@@ -131,6 +140,12 @@ def load_estimator(path, width, support=False):
         m = pickle.load(f)
     if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
         raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
+    if m.get("model") == "GBR":
+        model = gbr.load(m)
+        if model.width != width:
+            raise ValueError(f"{path}: the model takes {model.width} features, the cascade makes {width} "
+                             f"(num_class + 5 k: check --k and --dataset)")
+        return Estimator("gbr", width, model=model)
     if m.get("model") == "SVR" and not support:
         raise ValueError(f"{path}: an SVR file holds support vectors, and the cascade does not predict from them "
                          f"yet; train --model LSVR, LR, EN, BR or CNN")
@@ -426,7 +441,7 @@ def getargs(argv=None):
     a = argparse.ArgumentParser(prog="edgeml_amd.offload")
     a.add_argument("img_dir", help="Directory of the images to run the cascade on.")
     a.add_argument("save_dir", help="Directory for the detections (<name>.npy) and offload.npz.")
-    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR / LSVR / SVR / KNR) or wts<fold>.pth (CNN).")
+    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR / LSVR / SVR / KNR / GBR) or wts<fold>.pth (CNN).")
     a.add_argument("--ratio", type=float, default=None, help="Offloading ratio: the threshold is test.py:35's on --estimates.")
     a.add_argument("--estimates", type=str, default=None, help="Directory holding estimate<fold>.npz (with --ratio).")
     a.add_argument("--threshold", type=float, default=None, help="Offload an image when its estimate exceeds this.")

@@ -64,6 +64,8 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_offload_gather", "edgedet_offload_flag",
            "edgedet_kmodel_prepare", "edgedet_kmodel_workspace_size", "edgedet_svr_model_predict",
            "edgedet_knn_model_predict",
+           "edgedet_gbr_workspace_size", "edgedet_gbr_prepare", "edgedet_gbr_fit", "edgedet_gbr_model_predict",
+           "edgedet_gbr_best_split",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
            "edgedet_model_prepare_host", "edgedet_model_forward", "edgedet_model_max_detections",
            "edgedet_model_records", "edgedet_ssdlite_workspace_size", "edgedet_ssdlite_forward",
@@ -190,6 +192,17 @@ def lib():
     for name in ("edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide",
                  "edgedet_offload_pack", "edgedet_offload_gather", "edgedet_offload_flag", "edgedet_kmodel_prepare",
                  "edgedet_svr_model_predict", "edgedet_knn_model_predict"):
+        getattr(L, name).restype = ctypes.c_int
+    L.edgedet_gbr_workspace_size.argtypes = [_vp, _i32, _i64]
+    L.edgedet_gbr_workspace_size.restype = _i64
+    L.edgedet_gbr_prepare.argtypes = [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]
+    L.edgedet_gbr_fit.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _dbl, _i32,
+                                  _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_gbr_best_split.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp]
+    L.edgedet_gbr_model_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _i32, _i32, _vp,
+                                            _vp]
+    for name in ("edgedet_gbr_prepare", "edgedet_gbr_fit", "edgedet_gbr_best_split", "edgedet_gbr_model_predict"):
         getattr(L, name).restype = ctypes.c_int
     _u64 = ctypes.c_uint64
     L.edgedet_model_weights_size.argtypes = [_i32, _i32, _i32]

@@ -555,6 +555,57 @@ int edgedet_knn_model_predict(const double* feat, int64_t B, int64_t D, const do
                               const double* z, const double* norm, const double* target, int64_t n, int32_t k,
                               void* ws, int64_t ws_bytes, double* est, int32_t* nbr, void* stream);
 
+/* ------------------------------------------------------------------ gradient boosting regressor (regression.py) */
+/*
+ * regression.py's GradientBoostingRegressor(learning_rate, n_estimators, subsample = 1.0) with max_depth 1..4
+ * and criterion friedman_mse behind fit_model's StandardScaler, every cross-validation fold in flight
+ * (csrc/gbr.hip).  The residuals of a stage are carried as integers rq = rint(r 2^q), so every
+ * residual sum is exact and a split's gain does not depend on the order of summation; among bit-equal gains
+ * the lowest feature wins, then the lowest threshold.  The caller owns every buffer; the launchers allocate
+ * nothing, do not synchronise and return -1 with edgedet_last_error set on a bad argument.
+ *
+ * x, N, D, tr_idx, tr_off_host, tr_off, folds, mean, scale are the estimator regressors' (every fold
+ * non-empty, 1 <= D <= 255).  Trees are stored in heap layout (children of node i at 2 i + 1, 2 i + 2):
+ * feature int16 [F][T][2^depth - 1] (-1 = leaf), threshold [F][T][2^depth - 1], value [F][T][2^(depth+1) - 1]
+ * (0 for a node that does not exist); a row goes right when double(z32) > threshold.
+ *
+ * edgedet_gbr_workspace_size: bytes of the workspace of edgedet_gbr_fit (and, with folds = 1 and tr_off_host =
+ * {0, n}, of edgedet_gbr_best_split); < 0 on bad sizes.  The workspace is 8-byte aligned.
+ */
+int64_t edgedet_gbr_workspace_size(const int64_t* tr_off_host, int32_t folds, int64_t D);
+/* z32 [F][N][D] = float((x - mean_f) / scale_f): a true float64 division, rounded to float32. */
+int edgedet_gbr_prepare(const double* x, int64_t N, int64_t D, const double* mean, const double* scale,
+                        int32_t folds, float* z32, void* stream);
+/* The whole fit, enqueued without a host round trip: per stage one scan launch and one select launch per tree
+ * level and one update launch.  y [F][N] the targets; pos [F][N] a row's position in its fold's training list
+ * (-1: a validation row); ord and sorted hold per fold f (at tr_off[f] * D) and feature j (at j * n_f) the
+ * training positions in the order of z32[:, j] (ties by position) and those values; init [F] = F0, the mean of
+ * the training targets; q [F] (host and device) the residual scale, 26 <= q <= 1000.  est [F][N] is the
+ * running F of every row and the estimates at the end; nodes [F][T] the split nodes per stage; tied [F] the
+ * split nodes with a second feature at the maximal gain; status [F]: 0, or the 1-based stage whose residuals
+ * reached 2^(62 - ceil(log2 n)) in magnitude (read it once, after the stream has drained). */
+int edgedet_gbr_fit(const float* z32, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
+                    const int32_t* pos, const int32_t* ord, const float* sorted, const int64_t* tr_off_host,
+                    const int64_t* tr_off, int32_t folds, const double* init, const int32_t* q_host, const int32_t* q,
+                    double learning_rate, int32_t T, int32_t depth, void* ws, int64_t ws_bytes, int16_t* feature,
+                    double* threshold, double* value, double* est, int32_t* nodes, int32_t* tied, int32_t* status,
+                    void* stream);
+/* One level's scan and arg-best of one fold, for a given map node [n] of training positions to nodes (a value
+ * >= nn: in no node) and residual quanta rq [n]: per node m < nn (nn = 1, 2, 4 or 8) the best candidate's
+ * feature (-1: no valid candidate), threshold, gain, left count wl and left sum Sl, leaf (1 when sklearn's rules
+ * other than the depth limit make the node a leaf) and tied (a second feature attains the gain). */
+int edgedet_gbr_best_split(const int32_t* ord, const float* sorted, int64_t n, int64_t D, const uint8_t* node,
+                           const int64_t* rq, int32_t nn, int32_t q, void* ws, int64_t ws_bytes, int32_t* feature,
+                           double* threshold, double* gain, int32_t* wl, int64_t* Sl, int32_t* leaf, int32_t* tied,
+                           void* stream);
+/* est [B] = init + lr v_1 + lr v_2 + ... of one fold's trees (feature, threshold [T][2^depth - 1], value
+ * [T][2^(depth+1) - 1]) on the rows of feat [B][D], standardised as edgedet_gbr_prepare does: the leaf values
+ * are gathered in parallel, the sum is formed in stage order with every product and sum rounded by itself, so
+ * the estimate equals the fit's bit for bit and does not depend on B. */
+int edgedet_gbr_model_predict(const double* feat, int64_t B, int64_t D, const double* mean, const double* scale,
+                              const int16_t* feature, const double* threshold, const double* value, double init,
+                              double learning_rate, int32_t T, int32_t depth, double* est, void* stream);
+
 /* ------------------------------------------------------------------ offloading cascade (csrc/offload.hip) */
 /*
  * The on-device decision chain between the weak and the strong detector (edgeml_amd.offload); every
