@@ -38,18 +38,23 @@ __device__ __forceinline__ float div_fast(float a, float b, float rb) {
 }
 
 template <typename T, bool FAST = false>
-__device__ __forceinline__ float pre_load(const T* src, int64_t i) {
-    if constexpr (sizeof(T) == 1) return FAST ? div_fast((float)src[i], 255.f, 1.f / 255.f) : (float)src[i] / 255.f;
-    else return src[i];
+__device__ __forceinline__ float pre_load(T raw) {
+    if constexpr (sizeof(T) == 1) return FAST ? div_fast((float)raw, 255.f, 1.f / 255.f) : (float)raw / 255.f;
+    else return raw;
 }
 
 // One output pixel of the transform (normalise, then bilinear resize with align_corners=False; ATen
-// area_pixel_compute_source_index) from image plane base xb [3][H][W]: the three channels and a zero
-// fourth.  Shared by the transform kernel and the SSD stem that folds the transform in, so both
-// produce the same bits.
-template <typename T, bool FAST = false>
-__device__ __forceinline__ f32x4 pre_pixel(const T* __restrict__ xb, int H, int W, float sh, float sw,
-                                           const float* mean, const float* stdv, const float* rstd, int oy, int ox) {
+// area_pixel_compute_source_index) in three steps, so that a caller with several pixels per thread can
+// issue every pixel's loads before the first arithmetic on any of them (the SSD stem): pre_coord (the
+// four source taps and the two weights), pre_taps (the 12 raw loads), pre_value (the arithmetic).
+// pre_pixel is their composition; the transform kernel and the stem share the one body of arithmetic,
+// so both produce the same bits.
+struct PreCoord {
+    int y0, y1, x0, x1;
+    float ly, lx;
+};
+
+__device__ __forceinline__ PreCoord pre_coord(int H, int W, float sh, float sw, int oy, int ox) {
     // ATen's CPU upsample_bilinear2d as built (contracted): src = fma(scale, dst + 0.5, -0.5), clamped
     // at 0; index = min(floor(src), size - 1); lambda = clamp(src - index, 0, 1); each linear step
     // fma(t0, lambda0, t1 * lambda1), width first (bit-identical to F.interpolate on the CPU oracle,
@@ -58,26 +63,59 @@ __device__ __forceinline__ f32x4 pre_pixel(const T* __restrict__ xb, int H, int 
     float rx = __builtin_fmaf(sw, (float)ox + 0.5f, -0.5f);
     ry = ry < 0.f ? 0.f : ry;
     rx = rx < 0.f ? 0.f : rx;
-    const int y0 = min((int)ry, H - 1), x0 = min((int)rx, W - 1);
-    const int y1 = y0 + ((y0 < H - 1) ? 1 : 0);
-    const int x1 = x0 + ((x0 < W - 1) ? 1 : 0);
-    const float ly = fminf(fmaxf(ry - (float)y0, 0.f), 1.f), lx = fminf(fmaxf(rx - (float)x0, 0.f), 1.f);
+    PreCoord k;
+    k.y0 = min((int)ry, H - 1);
+    k.x0 = min((int)rx, W - 1);
+    k.y1 = k.y0 + ((k.y0 < H - 1) ? 1 : 0);
+    k.x1 = k.x0 + ((k.x0 < W - 1) ? 1 : 0);
+    k.ly = fminf(fmaxf(ry - (float)k.y0, 0.f), 1.f);
+    k.lx = fminf(fmaxf(rx - (float)k.x0, 0.f), 1.f);
+    return k;
+}
+
+// raw[4 c + t]: taps t = (y0, x0), (y0, x1), (y1, x0), (y1, x1) of channel plane c; the four tap offsets
+// o[] (I = int64_t, or uint32_t where the caller has checked that 3 H W fits 31 bits) are shared by the
+// three planes, plane = H W
+template <typename T, typename I>
+__device__ __forceinline__ void pre_taps(const T* __restrict__ xb, I plane, const I (&o)[4], T (&raw)[12]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const T* src = xb + (I)c * plane;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) raw[4 * c + t] = src[o[t]];
+    }
+}
+
+template <typename T, bool FAST = false>
+__device__ __forceinline__ f32x4 pre_value(const T (&raw)[12], float ly, float lx, const float* mean, const float* stdv,
+                                           const float* rstd) {
     const float hy = 1.f - ly, hx = 1.f - lx;
     float v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const T* src = xb + (int64_t)c * H * W;
-        auto norm = [&](int64_t i) {
-            const float a = pre_load<T, FAST>(src, i) - mean[c];
+        auto norm = [&](T r) {
+            const float a = pre_load<T, FAST>(r) - mean[c];
             return FAST ? div_fast(a, stdv[c], rstd[c]) : a / stdv[c];
         };
-        const float a00 = norm((int64_t)y0 * W + x0);
-        const float a01 = norm((int64_t)y0 * W + x1);
-        const float a10 = norm((int64_t)y1 * W + x0);
-        const float a11 = norm((int64_t)y1 * W + x1);
+        const float a00 = norm(raw[4 * c]);
+        const float a01 = norm(raw[4 * c + 1]);
+        const float a10 = norm(raw[4 * c + 2]);
+        const float a11 = norm(raw[4 * c + 3]);
         v[c] = __builtin_fmaf(__builtin_fmaf(a00, hx, a01 * lx), hy, __builtin_fmaf(a10, hx, a11 * lx) * ly);
     }
     return f32x4{v[0], v[1], v[2], 0.f};
+}
+
+// from image plane base xb [3][H][W]: the three channels and a zero fourth
+template <typename T, bool FAST = false>
+__device__ __forceinline__ f32x4 pre_pixel(const T* __restrict__ xb, int H, int W, float sh, float sw,
+                                           const float* mean, const float* stdv, const float* rstd, int oy, int ox) {
+    const PreCoord k = pre_coord(H, W, sh, sw, oy, ox);
+    const int64_t o[4] = {(int64_t)k.y0 * W + k.x0, (int64_t)k.y0 * W + k.x1, (int64_t)k.y1 * W + k.x0,
+                          (int64_t)k.y1 * W + k.x1};
+    T raw[12];
+    pre_taps<T, int64_t>(xb, (int64_t)H * W, o, raw);
+    return pre_value<T, FAST>(raw, k.ly, k.lx, mean, stdv, rstd);
 }
 
 // Host: may the uint8 transform use div_fast?  Every operand a uint8 image can give either division
@@ -500,7 +538,8 @@ static int dwconv_rb_launch(const DwParams& p, hipStream_t s) {
 // features.0.0 (conv 3x3 s2, 3(+1 pad) -> 16, folded BN, hardswish) and features.0.1 (depthwise 3x3
 // 16 + BN + ReLU, projection 1x1 16 -> 16 + BN, + the stem output) in one pass: the two 16-channel
 // 160x160 tensors between them never reach HBM.  Block = one image, a 16 x 16 output tile:
-//   1. the 37 x 37 x 4 input tile (stride-2 receptive field of the 18 x 18 stem halo) into LDS;
+//   1. the 37 x 37 x 3 input tile (stride-2 receptive field of the 18 x 18 stem halo) into LDS, with
+//      the weights and two small index tables of the halo;
 //   2. stem outputs on the 18 x 18 halo (zero outside the map: the depthwise pads them) as a GEMM on
 //      the matrix cores, [324 halo pixels] x [36 = 9 taps x 4 channels] x [16], one
 //      v_mfma_f32_16x16x4_f32 per tap (exact fp32 products);
@@ -513,56 +552,132 @@ static int dwconv_rb_launch(const DwParams& p, hipStream_t s) {
 constexpr int STEM_T = 16, STEM_SH = STEM_T + 2, STEM_XH = 2 * STEM_SH + 1, STEM_SS = 20;
 // LDS weight image: w0 [16][36] (taps (kh, kw, ci)), b0 [16], wd [9][16], bd [16], w1 [16][16], b1 [16]
 constexpr int STEM_W0 = 0, STEM_B0 = 576, STEM_WD = 592, STEM_BD = 736, STEM_W1 = 752, STEM_B1 = 1008, STEM_NW = 1024;
+// LDS input tile: one plane of STEM_XP floats per channel, [37 rows][STEM_RP], a row as its 19 even
+// columns followed (from STEM_ODD) by its 18 odd ones.  The halo GEMM reads, per tap, channel q4 of 16
+// consecutive halo pixels: in this layout one float apart within a halo row, the next halo row
+// 2 STEM_RP = 2 (mod 16) further and the next channel STEM_XP = 16 (mod 32) further, so the 32 lanes of
+// a ds_read_b32 group fall on 32 different banks (pixel-major NHWC4 had them 8 floats apart: 4-way
+// conflicts, 559 conflict cycles per wave).  The zero fourth channel is not stored: its lanes read
+// STEM_NZ zeros kept behind the planes (from STEM_XZ; one address, a broadcast).
+constexpr int STEM_RP = 41, STEM_ODD = 19, STEM_XP = 1520, STEM_XZ = 3 * STEM_XP, STEM_NZ = 104;
+constexpr int STEM_NV = STEM_SH * STEM_SH, STEM_NTL = (STEM_NV + 15) / 16, STEM_NVP = 16 * STEM_NTL;
+static_assert(STEM_XH * STEM_RP <= STEM_XP && 2 * STEM_RP + STEM_ODD < STEM_NZ && STEM_XZ >= 256 * 17, "stem LDS layout");
 
-// T = float: the transform's NHWC4 output (p.x); T = float / uint8_t with FUSED: the source image
-// (p.src / p.src8, [B][3][H0][W0]) and the transform computed per input pixel of the tile (pre_pixel,
-// the same bits as the transform kernel): no transform launch and no NHWC4 round trip through HBM.
+// T = float: the transform's NHWC4 output (p.x; its fourth channel is the transform's zero pad and is
+// taken as zero, not read); T = float / uint8_t with FUSED: the source image (p.src / p.src8,
+// [B][3][H0][W0]) and the transform computed per input pixel of the tile (pre_coord / pre_taps /
+// pre_value, the same bits as the transform kernel): no transform launch and no NHWC4 round trip
+// through HBM.
 template <typename T, bool FUSED, bool FAST = false>
 __global__ void __launch_bounds__(256) ssd_stem_kernel(StemParams p, int tiles_w) {
-    __shared__ __attribute__((aligned(16))) float xs[STEM_XH * STEM_XH * 4];
+    __shared__ __attribute__((aligned(16))) float xs[STEM_XZ + STEM_NZ];
     __shared__ __attribute__((aligned(16))) float ss[STEM_SH * STEM_SH * STEM_SS];
     __shared__ __attribute__((aligned(16))) float ws[STEM_NW];
+    __shared__ __attribute__((aligned(16))) uint32_t msk[STEM_NVP];  // halo pixel inside the stem map: all ones, else 0
+    __shared__ int atab[STEM_NVP];                                   // halo pixel -> offset of its tap (0, 0) in a plane
     const int tid = threadIdx.x, b = blockIdx.y;
     const int oh0 = (blockIdx.x / tiles_w) * STEM_T, ow0 = (blockIdx.x % tiles_w) * STEM_T;
     const int sh0 = oh0 - 1, sw0 = ow0 - 1;          // stem-output halo origin
     const int xh0 = 2 * sh0 - 1, xw0 = 2 * sw0 - 1;  // input tile origin (stem pad 1, stride 2)
     const float* xb = FUSED ? nullptr : p.x + (int64_t)b * p.H * p.W * 4;
-    {  // all of a thread's input pixels and weights in flight at once (one memory round trip)
+    {
+        // One memory round trip: the weights and every input pixel of the thread (six rounds of 256 over
+        // the 37 x 37 tile) are loaded unconditionally, all loads issued before the first use of any.  A
+        // pixel outside the resized image, or a round past the tile's last pixel, loads a clamped pixel
+        // instead (no branch around a load); the former is zeroed by a select after the arithmetic, the
+        // latter is the tile's last pixel again and stores the same value to the same place.
+        constexpr int NX = STEM_XH * STEM_XH, R = (NX + 255) / 256;
+        // The transform's coordinate step is separable: once per tile row and per tile column (74 threads,
+        // pre_coord as it is, on the row / column clamped into the resized image), kept in the LDS space of
+        // the stem outputs (idle until phase 2) as {offset of tap 0, of tap 1, weight, place in the LDS
+        // plane + STEM_OUT if outside the image}; a pixel adds its row's and its column's entry.
+        constexpr int STEM_OUT = 1 << 29;
+        [[maybe_unused]] int4* ct = reinterpret_cast<int4*>(ss);  // [37 rows][37 columns]
+        if constexpr (FUSED) {
+            if (tid < 2 * STEM_XH) {
+                const bool isrow = tid < STEM_XH;
+                const int i = isrow ? tid : tid - STEM_XH;
+                const int g = (isrow ? xh0 : xw0) + i, n = isrow ? p.H : p.W, gc = min(max(g, 0), n - 1);
+                const PreCoord k = pre_coord(p.H0, p.W0, p.sh, p.sw, gc, gc);
+                const int place = (isrow ? i * STEM_RP : (i & 1) * STEM_ODD + (i >> 1)) + ((unsigned)g < (unsigned)n ? 0 : STEM_OUT);
+                ct[tid] = isrow ? make_int4(k.y0 * p.W0, k.y1 * p.W0, __float_as_int(k.ly), place)
+                                : make_int4(k.x0, k.x1, __float_as_int(k.lx), place);
+            }
+            __syncthreads();
+        }
         float wv[STEM_NW / 256];
+        __builtin_assume(tid >= 0 && tid < 256);
 #pragma unroll
         for (int r = 0; r < STEM_NW / 256; ++r) {
-            const int e = tid + 256 * r;
-            const float* src = e < STEM_B0   ? p.w0 + (e / 36) * p.ld0 + e % 36
-                               : e < STEM_WD ? p.b0 + (e - STEM_B0)
-                               : e < STEM_BD ? p.wd + (e - STEM_WD)
-                               : e < STEM_W1 ? p.bd + (e - STEM_BD)
-                               : e < STEM_B1 ? p.w1 + ((e - STEM_W1) / 16) * p.ld1 + (e - STEM_W1) % 16
-                                             : p.b1 + (e - STEM_B1);
-            wv[r] = *src;
+            // element e of the LDS weight image: its array (a uniform base) and its offset there, each by
+            // selects, no branch chain; the rounds are compile-time, so most of the tests fold
+            const int e = tid + 256 * r, e1 = max(e - STEM_W1, 0);
+            const int o_w1 = (e1 >> 4) * p.ld1 + (e1 & 15), o_w0 = (e / 36) * p.ld0 + e % 36;
+            const int o_bd = e - STEM_BD, o_wd = e - STEM_WD, o_b0 = e - STEM_B0;
+            const bool c_w1 = r >= STEM_W1 / 256 && e < STEM_B1, c_bd = r == STEM_W1 / 256 && e < STEM_W1;
+            const bool c_wd = r == STEM_BD / 256 && e < STEM_BD, c_b0 = r == STEM_WD / 256 && e < STEM_WD;
+            const bool c_w0 = r <= STEM_B0 / 256 && e < STEM_B0;
+            const float* base = p.b1;
+            int off = e - STEM_B1;
+            base = c_w1 ? p.w1 : base, off = c_w1 ? o_w1 : off;
+            base = c_bd ? p.bd : base, off = c_bd ? o_bd : off;
+            base = c_wd ? p.wd : base, off = c_wd ? o_wd : off;
+            base = c_b0 ? p.b0 : base, off = c_b0 ? o_b0 : off;
+            base = c_w0 ? p.w0 : base, off = c_w0 ? o_w0 : off;
+            wv[r] = base[off];
         }
-        constexpr int R = (STEM_XH * STEM_XH + 255) / 256;
+        int xi[R];
+        bool inb[R];
+        [[maybe_unused]] float ly[R], lx[R];
+        [[maybe_unused]] T raw[R][12];
         f32x4 xv[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int v = tid + 256 * r;
-            const int ih = xh0 + v / STEM_XH, iw = xw0 + v % STEM_XH;
-            const bool in = v < STEM_XH * STEM_XH && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+            const int v = min(tid + 256 * r, NX - 1);
+            const int row = v / STEM_XH, col = v - row * STEM_XH;
             if constexpr (FUSED) {
+                // 32-bit tap offsets, one per tap for the three planes, on the image's (uniform) base: the
+                // launcher checks that 3 H0 W0 fits 31 bits
                 const T* img = (const T*)(sizeof(T) == 1 ? (const void*)p.src8 : (const void*)p.src) +
                                (int64_t)b * 3 * p.H0 * p.W0;
-                xv[r] = in ? pre_pixel<T, FAST>(img, p.H0, p.W0, p.sh, p.sw, p.mean, p.stdv, p.rstd, ih, iw)
-                           : f32x4{0.f, 0.f, 0.f, 0.f};
+                const int4 ky = ct[row], kx = ct[STEM_XH + col];
+                const uint32_t o[4] = {(uint32_t)(ky.x + kx.x), (uint32_t)(ky.x + kx.y), (uint32_t)(ky.y + kx.x),
+                                       (uint32_t)(ky.y + kx.y)};
+                pre_taps<T, uint32_t>(img, (uint32_t)(p.H0 * p.W0), o, raw[r]);
+                ly[r] = __int_as_float(ky.z);
+                lx[r] = __int_as_float(kx.z);
+                inb[r] = ky.w + kx.w < STEM_OUT;
+                xi[r] = (ky.w + kx.w) & (STEM_OUT - 1);
             } else {
-                const float* src = xb + (in ? ((int64_t)ih * p.W + iw) * 4 : 0);  // clamped: loads stay unconditional
-                xv[r] = *reinterpret_cast<const f32x4*>(src);
-                if (!in) xv[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+                const int ih = xh0 + row, iw = xw0 + col;
+                inb[r] = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+                xi[r] = row * STEM_RP + (col & 1) * STEM_ODD + (col >> 1);
+                const float* src = xb + (inb[r] ? ((int64_t)ih * p.W + iw) * 4 : 0);
+                xv[r] = f32x4{src[0], src[1], src[2], 0.f};  // one 12-byte load: the pad channel is not fetched
             }
         }
+        __builtin_amdgcn_sched_barrier(0);  // nothing below moves above the loads, and no load below this line
+        // while the loads are in flight: the index tables of the 18 x 18 halo (pixels past the 324th repeat
+        // the last one, as rows of the last 16-row GEMM tile) and the fourth channel's zeros
 #pragma unroll
-        for (int r = 0; r < R; ++r)
-            if (tid + 256 * r < STEM_XH * STEM_XH) *reinterpret_cast<f32x4*>(xs + 4 * (tid + 256 * r)) = xv[r];
+        for (int r = 0; r < (STEM_NVP + 255) / 256; ++r) {
+            const int e = tid + 256 * r;
+            if (e < STEM_NVP) {
+                const int v = min(e, STEM_NV - 1), vh = v / STEM_SH, vw = v - vh * STEM_SH;
+                const bool in = e < STEM_NV && (unsigned)(sh0 + vh) < (unsigned)p.Ho && (unsigned)(sw0 + vw) < (unsigned)p.Wo;
+                msk[e] = in ? 0xffffffffu : 0u;
+                atab[e] = 2 * vh * STEM_RP + vw;
+            }
+        }
+        if (tid < STEM_NZ) xs[STEM_XZ + tid] = 0.f;
 #pragma unroll
         for (int r = 0; r < STEM_NW / 256; ++r) ws[tid + 256 * r] = wv[r];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if constexpr (FUSED) xv[r] = pre_value<T, FAST>(raw[r], ly[r], lx[r], p.mean, p.stdv, p.rstd);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) xs[c * STEM_XP + xi[r]] = inb[r] ? xv[r][c] : 0.f;
+        }
     }
     __syncthreads();
     const int lane = tid & 63, wid = tid >> 6, l16 = lane & 15, q4 = lane >> 4;
@@ -573,29 +688,35 @@ __global__ void __launch_bounds__(256) ssd_stem_kernel(StemParams p, int tiles_w
 #pragma unroll
     for (int t = 0; t < 9; ++t) wb[t] = ws[STEM_W0 + l16 * 36 + 4 * t + q4];
     const float b0v = ws[STEM_B0 + l16];
-    constexpr int NV = STEM_SH * STEM_SH, NTL = (NV + 15) / 16;
-    for (int tl = wid; tl < NTL; tl += 4) {
-        const int va = min(16 * tl + l16, NV - 1);  // this lane's A row (pad rows repeat the last pixel)
-        const int lh = va / STEM_SH, lw = va - lh * STEM_SH;
+    // No index arithmetic in the tile loop: a lane's A row comes from atab (one read per tile), its nine
+    // taps are compile-time offsets from it, and the four outputs of a lane are consecutive halo pixels,
+    // zeroed outside the map by an AND with their msk words (one 16-byte read).
+    constexpr int NJ = (STEM_NTL + 3) / 4;
+    int a0[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        a0[j] = q4 == 3 ? STEM_XZ : atab[16 * min(wid + 4 * j, STEM_NTL - 1) + l16] + q4 * STEM_XP;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int tl = wid + 4 * j;
+        if (tl >= STEM_NTL) break;  // wave-uniform: the 21st tile is wave 0's
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const float av = xs[4 * ((2 * lh + t / 3) * STEM_XH + 2 * lw + t % 3) + q4];
+            const float av = xs[a0[j] + (t / 3) * STEM_RP + (t % 3 == 1 ? STEM_ODD : t % 3 / 2)];
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wb[t], acc, 0, 0, 0);
         }
+        const int v0 = 16 * tl + 4 * q4;  // STEM_NV is a multiple of 4: a lane's four pixels exist together
+        if (v0 < STEM_NV) {
+            const uint4 m = *reinterpret_cast<const uint4*>(msk + v0);
+            const uint32_t mi[4] = {m.x, m.y, m.z, m.w};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = 16 * tl + 4 * q4 + i;
-            if (v < NV) {
-                const int vh = v / STEM_SH, vw = v - vh * STEM_SH;
-                const bool in = (unsigned)(sh0 + vh) < (unsigned)p.Ho && (unsigned)(sw0 + vw) < (unsigned)p.Wo;
-                ss[v * STEM_SS + l16] = in ? apply_act(acc[i] + b0v, ACT_HSWISH) : 0.f;
-            }
+            for (int i = 0; i < 4; ++i)
+                ss[(v0 + i) * STEM_SS + l16] = __uint_as_float(__float_as_uint(apply_act(acc[i] + b0v, ACT_HSWISH)) & mi[i]);
         }
     }
     __syncthreads();
     const int lh = tid / STEM_T, lw = tid % STEM_T;
-    const int oh = oh0 + lh, ow = ow0 + lw;
     // depthwise on the vector ALUs (one output pixel x 16 channels per thread, taps (kh, kw)), its
     // outputs through LDS (the input tile's space, free now) into the projection GEMM on the matrix
     // cores: rows = the wave's 64 pixels in 4 tiles, columns = 16 channels, K = 16 in 4 steps
@@ -603,8 +724,7 @@ __global__ void __launch_bounds__(256) ssd_stem_kernel(StemParams p, int tiles_w
 #pragma unroll
     for (int c = 0; c < 16; ++c) dv[c] = 0.f;
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-        if ((unsigned)(oh - 1 + kh) >= (unsigned)p.Ho) continue;
+    for (int kh = 0; kh < 3; ++kh) {  // halo rows outside the map hold zeros: their taps add +-0, no test
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
             const float* sv = ss + ((lh + kh) * STEM_SH + lw + kw) * STEM_SS;
@@ -621,6 +741,17 @@ __global__ void __launch_bounds__(256) ssd_stem_kernel(StemParams p, int tiles_w
 #pragma unroll
     for (int k = 0; k < 4; ++k) w1v[k] = ws[STEM_W1 + l16 * 16 + 4 * k + q4];
     const float b1v = ws[STEM_B1 + l16];
+    // A GEMM tile is one row of the 16 x 16 output tile (row 4 wid + tl, uniform in the wave); a lane holds
+    // channel l16 of its pixels 4 q4 .. 4 q4 + 3.  Everything that depends on the lane alone is formed
+    // once: the column tests, the place of the residual (the stem output under the pixel, always inside
+    // ss: read without a test, all four before the first use) and the lane's offset in an output row.
+    const int wu = __builtin_amdgcn_readfirstlane(wid);
+    float* yb = p.y + (((int64_t)b * p.Ho + oh0 + 4 * wu) * p.Wo + ow0) * 16;  // the wave's first output pixel (uniform)
+    const float* rs = ss + ((4 * wid + 1) * STEM_SH + 4 * q4 + 1) * STEM_SS + l16;
+    const uint32_t yl = (uint32_t)(4 * q4 * 16 + l16);
+    bool okw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) okw[i] = ow0 + 4 * q4 + i < p.Wo;
     __syncthreads();
 #pragma unroll
     for (int tl = 0; tl < 4; ++tl) {
@@ -629,14 +760,15 @@ __global__ void __launch_bounds__(256) ssd_stem_kernel(StemParams p, int tiles_w
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dsm[(row0 + l16) * DS + 4 * k + q4], w1v[k], acc, 0, 0, 0);
+        float r[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = rs[(tl * STEM_SH + i) * STEM_SS];
+        const bool okh = oh0 + 4 * wu + tl < p.Ho;
+        float* yt = yb + (int64_t)tl * p.Wo * 16;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int px = row0 + 4 * q4 + i, ph = px / STEM_T, pw = px % STEM_T;
-            const int yh = oh0 + ph, yw = ow0 + pw;
-            if (yh < p.Ho && yw < p.Wo) {
-                const float r = ss[((ph + 1) * STEM_SH + pw + 1) * STEM_SS + l16];
-                p.y[(((int64_t)b * p.Ho + yh) * p.Wo + yw) * 16 + l16] = (acc[i] + b1v) + r;
-            }
+            const float o = (acc[i] + b1v) + r[i];
+            if (okh && okw[i]) yt[yl + 16 * i] = o;  // within one output row: 32 bits
         }
     }
 }
@@ -648,6 +780,8 @@ int ssd_stem_launch(const StemParams& p0, hipStream_t s) {
     EDGEDET_REQUIRE(!(p.src && p.src8), "ssd_stem: one source image (float or uint8)");
     if (fused) {
         EDGEDET_REQUIRE(p.H0 >= 1 && p.W0 >= 1, "ssd_stem: source image size");
+        // the kernel's tap offsets within one image are 32-bit (the per-image base stays 64-bit)
+        EDGEDET_REQUIRE(3 * (int64_t)p.H0 * p.W0 < ((int64_t)1 << 31), "ssd_stem: source image too large (3 H0 W0 must fit 31 bits)");
         p.sh = (float)p.H0 / (float)p.H;  // as the transform kernel's input / output scales
         p.sw = (float)p.W0 / (float)p.W;
     }
