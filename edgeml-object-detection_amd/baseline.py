@@ -81,11 +81,6 @@ def model_path(directory, fold):
     return os.path.join(directory, f"wts{fold + 1}.pickle")
 
 
-def _need_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("edgeml_amd.baseline needs an MI355X (HIP) device; there is no CPU path")
-
-
 def _train_lists(split):
     tr = [np.nonzero(~m)[0].astype(np.int32) for m in split]
     off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
@@ -103,7 +98,7 @@ def fit_dcsb_folds(dets, label_num, reward01, split, device="cuda"):
     dets[i] = (conf, area) of image i, label_num [N], reward01 [N] in {0, 1}.  Returns (results,
     models): per fold {train_est, val_est (int64), train_time, val_time} and the reference's model tuple
     (conf_thresh, num_thresh, area_thresh)."""
-    _need_device()
+    ops.need_device("edgeml_amd.baseline")
     split = np.asarray(split, dtype=bool)
     k, N = split.shape
     assert len(dets) == N and len(label_num) == N and len(reward01) == N
@@ -161,7 +156,7 @@ def fit_af_folds(features, reward01, split, positive_weight=3.0, device="cuda"):
     """fit_af for every fold of `split` at once.  Returns (results, models): per fold {train_est, val_est
     (int64), train_time, val_time} and {"coef" [D], "intercept", "classes", "positive_weight",
     "n_iter", "grad_norm"} (the last two: Newton steps taken and the final |grad f|)."""
-    _need_device()
+    ops.need_device("edgeml_amd.baseline")
     split = np.asarray(split, dtype=bool)
     k, N = split.shape
     y = np.asarray(reward01).astype(np.int32)
@@ -220,7 +215,7 @@ def _save_model(directory, fold, model):
 
 def main(opts):
     """baseline.py:161-204."""
-    _need_device()
+    ops.need_device("edgeml_amd.baseline")
     with np.load(opts.reward_path, allow_pickle=False) as z:
         reward = np.where(z["reward"] > 0, 1, 0)
     split = np.load(opts.split_path, allow_pickle=False)

@@ -24,6 +24,7 @@
 //   H[j][.] = e_j and gradient v_j, so its weight stays exactly 0 from a zero start.
 #include <vector>
 
+#include "fold_math.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
@@ -54,18 +55,6 @@ struct DcsbParams {
     int n_grid;
 };
 
-// fixed-order sum over the workgroup (every thread gets it)
-__device__ __forceinline__ long long dcsb_block_sum(long long v, long long* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = DCSB_NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ void __launch_bounds__(DCSB_NT) dcsb_fit_kernel(DcsbParams p) {
     const int fold = blockIdx.x, tid = threadIdx.x;
     __shared__ long long red[DCSB_NT];
@@ -79,7 +68,7 @@ __global__ void __launch_bounds__(DCSB_NT) dcsb_fit_kernel(DcsbParams p) {
 
     long long lab = 0;
     for (int64_t r = tid; r < ntr; r += DCSB_NT) lab += p.label_num[tr[r]];
-    const long long sum_label = dcsb_block_sum(lab, red);
+    const long long sum_label = block_sum<DCSB_NT>(lab, red);
 
     // (1) bisection: low = mid when count(conf > mid) - sum(label) >= 0, otherwise high = mid
     double low = 0.0, high = 1.0, mid = 0.0;
@@ -92,7 +81,7 @@ __global__ void __launch_bounds__(DCSB_NT) dcsb_fit_kernel(DcsbParams p) {
             const int64_t i = tr[r];
             for (int64_t j = p.det_off[i]; j < p.det_off[i + 1]; ++j) c += p.conf[j] > mid ? 1 : 0;
         }
-        const long long diff = dcsb_block_sum(c, red) - sum_label;
+        const long long diff = block_sum<DCSB_NT>(c, red) - sum_label;
         if (diff >= 0)
             low = mid;
         else
@@ -210,8 +199,6 @@ constexpr int SVM_NT = 1024;
 constexpr int SVM_MAXD = 256;  // padded width (features + bias)
 constexpr int SVM_LS_MAX = 40;  // halvings of the line search
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 struct SvmWs {  // the per-call workspace, carved out of one buffer
     double* H;     // [F][Dp][Dp]
     double* d;     // [T] decision value of every training row (T = tr_off[F])
@@ -252,17 +239,6 @@ struct SvmParams {
     int Dp;
 };
 
-__device__ __forceinline__ double svm_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = SVM_NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // out[r] = x[idx[r]] . vec for r < n: sixteen lanes per row (128-byte loads), butterfly sum.
 __device__ __forceinline__ void svm_rows_dot(const double* __restrict__ x, int Dp, const int32_t* __restrict__ idx,
                                              int64_t n, const double* vec, double* __restrict__ out) {
@@ -274,10 +250,7 @@ __device__ __forceinline__ void svm_rows_dot(const double* __restrict__ x, int D
         double acc = 0.0;
         if (ok)
             for (int k = sub; k < Dp; k += 16) acc += row[k] * vec[k];
-        acc += __shfl_xor(acc, 8, 16);
-        acc += __shfl_xor(acc, 4, 16);
-        acc += __shfl_xor(acc, 2, 16);
-        acc += __shfl_xor(acc, 1, 16);
+        acc = lane16_sum(acc);
         if (ok && sub == 0) out[r] = acc;
     }
 }
@@ -307,7 +280,7 @@ __global__ void __launch_bounds__(SVM_NT) svm_eval_kernel(SvmParams p) {
         q[r] = act ? 2.0 * C * s * h : 0.0;
         loss += act ? C * h * h : 0.0;
     }
-    loss = svm_block_sum(loss, red);  // also orders the q stores before the loads below
+    loss = block_sum<SVM_NT>(loss, red);  // also orders the q stores before the loads below
     // gradient g = v - X~^T q: a column per thread, four row groups summed in a fixed order
     const int col = tid & (SVM_MAXD - 1), rg = tid >> 8;
     double acc = 0.0;
@@ -457,7 +430,7 @@ __global__ void __launch_bounds__(SVM_NT) svm_step_kernel(SvmParams p) {
     double* q = p.ws.q + t0;
     const double* d = p.ws.d + t0;
     svm_rows_dot(p.x, Dp, idx, n, sy, q);
-    const double gp = svm_block_sum(tid < Dp ? g[tid] * sy[tid] : 0.0, red);  // also orders the q stores
+    const double gp = block_sum<SVM_NT>(tid < Dp ? g[tid] * sy[tid] : 0.0, red);  // also orders the q stores
     const double f0 = p.ws.f[fold];
     const double slack = 16.0 * 2.220446049250313e-16 * fabs(f0);
     double t = 1.0;
@@ -474,7 +447,7 @@ __global__ void __launch_bounds__(SVM_NT) svm_step_kernel(SvmParams p) {
             const double h = 1.0 - s * (d[r] + t * q[r]);
             part += h > 0.0 ? C * h * h : 0.0;
         }
-        const double fn = svm_block_sum(part, red);
+        const double fn = block_sum<SVM_NT>(part, red);
         ok = fn <= f0 + 1e-4 * t * gp + slack;
         if (!ok) t *= 0.5;
     }

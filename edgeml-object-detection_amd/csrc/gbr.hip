@@ -30,6 +30,7 @@
 //                       stages gathered in parallel, lr * value added to init in stage order by one thread.
 #include <cstdint>
 
+#include "fold_math.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
@@ -39,7 +40,6 @@ constexpr int GBR_SCAN_W = 8;     // waves that share one (fold, feature) list
 constexpr int GBR_SCAN_NT = 64 * GBR_SCAN_W;
 constexpr int GBR_NODES = 8;      // live nodes of one scanned level: depth <= 4
 constexpr int GBR_MAXDEPTH = 4;
-constexpr int GBR_MAXD = 255;
 constexpr int GBR_PRED_STAGES = 1024;
 constexpr int GBR_QMIN = 26, GBR_QMAX = 1000;
 constexpr uint8_t GBR_DEAD = 255;  // a training row that sits in a finished leaf
@@ -510,7 +510,7 @@ __global__ void __launch_bounds__(GBR_NT) gbr_predict_kernel(const double* __res
                                                              const double* __restrict__ threshold,
                                                              const double* __restrict__ value, double init, double lr,
                                                              int T, int depth, double* __restrict__ est) {
-    __shared__ float z[GBR_MAXD + 1];
+    __shared__ float z[FOLD_MAXD];
     __shared__ double step[GBR_PRED_STAGES];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
@@ -565,15 +565,6 @@ static GbrWs gbr_ws(void* base, int64_t rows, int64_t folds, int64_t D) {
     return w;
 }
 
-static bool gbr_folds_ok(const int64_t* tr_off_host, int32_t folds) {
-    if (!tr_off_host || folds < 1 || folds > 65535 || tr_off_host[0] != 0) return false;
-    for (int f = 0; f < folds; ++f) {
-        const int64_t n = tr_off_host[f + 1] - tr_off_host[f];
-        if (n < 1 || n >= ((int64_t)1 << 31)) return false;
-    }
-    return true;
-}
-
 static int gbr_launch_scan(int nn, int D, int folds, const int32_t* ord, const float* sv, const int64_t* tr_off,
                            int64_t n1, const uint8_t* node, const int64_t* rq, const GbrWs& w, hipStream_t st) {
     const dim3 grid((unsigned)((int64_t)folds * D)), block(GBR_SCAN_NT);
@@ -596,13 +587,13 @@ static int gbr_launch_scan(int nn, int D, int folds, const int32_t* ord, const f
 using namespace edgedet;
 
 extern "C" int64_t edgedet_gbr_workspace_size(const int64_t* tr_off_host, int32_t folds, int64_t D) {
-    if (!gbr_folds_ok(tr_off_host, folds) || D < 1 || D > GBR_MAXD) return -1;
+    if (!folds_ok(tr_off_host, folds, 0, true, INT32_MAX) || !fold_dims_ok(D)) return -1;
     return gbr_ws(nullptr, tr_off_host[folds], folds, D).bytes;
 }
 
 extern "C" int edgedet_gbr_prepare(const double* x, int64_t N, int64_t D, const double* mean, const double* scale,
                                    int32_t folds, float* z32, void* stream) {
-    EDGEDET_REQUIRE(D >= 1 && D <= GBR_MAXD && N >= 1 && N < ((int64_t)1 << 31) && folds >= 1 && folds <= 65535,
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1 && N < ((int64_t)1 << 31) && folds >= 1 && folds <= 65535,
                     "gbr_prepare: 1 <= features <= 255, 1 <= rows < 2^31, 1 <= folds <= 65535");
     EDGEDET_REQUIRE(x && mean && scale && z32, "gbr_prepare: null pointer");
     hipLaunchKernelGGL(gbr_prepare_kernel, dim3((unsigned)cdiv(N * D, GBR_NT), (unsigned)folds), dim3(GBR_NT), 0,
@@ -617,9 +608,10 @@ extern "C" int edgedet_gbr_fit(const float* z32, int64_t N, int64_t D, const dou
                                const int32_t* q_host, const int32_t* q, double learning_rate, int32_t T, int32_t depth,
                                void* ws, int64_t ws_bytes, int16_t* feature, double* threshold, double* value,
                                double* est, int32_t* nodes, int32_t* tied, int32_t* status, void* stream) {
-    EDGEDET_REQUIRE(D >= 1 && D <= GBR_MAXD && N >= 1 && N < ((int64_t)1 << 31),
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1 && N < ((int64_t)1 << 31),
                     "gbr_fit: 1 <= features <= 255, 1 <= rows < 2^31");
-    EDGEDET_REQUIRE(gbr_folds_ok(tr_off_host, folds), "gbr_fit: every fold needs 1 to 2^31 - 1 training rows");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, 0, true, INT32_MAX),
+                    "gbr_fit: every fold needs 1 to 2^31 - 1 training rows");
     EDGEDET_REQUIRE(depth >= 1 && depth <= GBR_MAXDEPTH && T >= 1, "gbr_fit: 1 <= max_depth <= 4, n_estimators >= 1");
     EDGEDET_REQUIRE(z32 && y && tr_idx && pos && ord && sorted && tr_off && init && q_host && q && ws && feature &&
                         threshold && value && est && nodes && tied && status,
@@ -659,7 +651,7 @@ extern "C" int edgedet_gbr_best_split(const int32_t* ord, const float* sorted, i
                                       const uint8_t* node, const int64_t* rq, int32_t nn, int32_t q, void* ws,
                                       int64_t ws_bytes, int32_t* feature, double* threshold, double* gain, int32_t* wl,
                                       int64_t* Sl, int32_t* leaf, int32_t* tied, void* stream) {
-    EDGEDET_REQUIRE(D >= 1 && D <= GBR_MAXD && n >= 1 && n < ((int64_t)1 << 31),
+    EDGEDET_REQUIRE(fold_dims_ok(D) && n >= 1 && n < ((int64_t)1 << 31),
                     "gbr_best_split: 1 <= features <= 255, 1 <= rows < 2^31");
     EDGEDET_REQUIRE(nn == 1 || nn == 2 || nn == 4 || nn == 8, "gbr_best_split: 1, 2, 4 or 8 nodes");
     EDGEDET_REQUIRE(q >= GBR_QMIN && q <= GBR_QMAX, "gbr_best_split: 26 <= q <= 1000");
@@ -689,7 +681,7 @@ extern "C" int edgedet_gbr_model_predict(const double* feat, int64_t B, int64_t 
                                          const double* scale, const int16_t* feature, const double* threshold,
                                          const double* value, double init, double learning_rate, int32_t T,
                                          int32_t depth, double* est, void* stream) {
-    EDGEDET_REQUIRE(D >= 1 && D <= GBR_MAXD && B >= 1 && B < ((int64_t)1 << 31),
+    EDGEDET_REQUIRE(fold_dims_ok(D) && B >= 1 && B < ((int64_t)1 << 31),
                     "gbr_model_predict: 1 <= features <= 255, 1 <= rows < 2^31");
     EDGEDET_REQUIRE(depth >= 1 && depth <= GBR_MAXDEPTH && T >= 1,
                     "gbr_model_predict: 1 <= max_depth <= 4, n_estimators >= 1");

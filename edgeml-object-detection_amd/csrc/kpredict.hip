@@ -3,15 +3,15 @@
 // fixed-order sums, no float atomics.  An estimate is a function of (feature row, model) only: it does not
 // depend on the batch the row arrives in or on its place in that batch.
 //
-//   kp_prepare_kernel   once per loaded model: Z = (x - mean) * (1 / scale) of the stored rows and |z|^2 of
-//                       each, in svr_std_kernel's order (sixteen lanes per row, k = sub, sub + 16, ..., a
-//                       butterfly of 8, 4, 2, 1), which is knn_norm_kernel's order too.
+//   kp_prepare_kernel   once per loaded model: Z = zscore(x, mean, 1 / scale) of the stored rows and |z|^2 of
+//                       each: sixteen lanes per row, k = sub, sub + 16, ..., then lane16_sum (fold_math.hpp),
+//                       as svr_std_kernel and knn_norm_kernel take them.
 //   kp_tile_kernel      a workgroup per (64 stored rows x 16 queries), a wave per 16 x 16 tile.  The sixteen
-//                       queries are standardised into LDS by the same expression and their norms taken in that
-//                       same sixteen-lane order; the dot products come from v_mfma_f64_16x16x4_f64 with k
-//                       ascending in steps of four, operands past D, n or B zero; d = max((nq + nb) - 2 acc, 0):
-//                       knn_dist_kernel's chain per pair (csrc/regress.hip), so a pair's distance is the fit's
-//                       bit for bit wherever the pair sits in a tile.
+//                       queries are standardised into LDS by zscore and their norms taken in that same
+//                       sixteen-lane order; the dot products come from v_mfma_f64_16x16x4_f64 with k ascending
+//                       in steps of four, operands past D, n or B zero; d = sqdist(nq, nb, acc).  The fits
+//                       (knn_dist_kernel, svr_kmat_kernel) call the same three functions on the same k order,
+//                       so a pair's distance is the fit's bit for bit wherever the pair sits in a tile.
 //                         KNR: d goes to the workspace [B][n].
 //                         SVR: beta_j exp(-gamma d), the tile's sixteen stored columns added by a butterfly
 //                              into one partial per (query, tile) in the workspace [B][tiles].
@@ -24,21 +24,18 @@
 //                       (a wave sum, then the four waves).
 #include <cstdint>
 
+#include "fold_math.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
 
 constexpr int KP_STD_NT = 1024;
 constexpr int KP_NT = 256;
-constexpr int KP_MAXD = 256;
-constexpr int KP_LD = KP_MAXD + 2;  // LDS row stride of the query tile: a half wave's 8-byte reads hit 32 bank pairs
+constexpr int KP_LD = FOLD_MAXD + 2;  // LDS row stride of the query tile: a half wave's 8-byte reads hit 32 bank pairs
 constexpr int KP_SEL_NT = 256;
 constexpr int KP_SEL_KEYS = 16;  // keys a selection thread holds in registers: up to 4,096 stored rows
 constexpr int KIND_SVR = 0, KIND_KNR = 1;
 
-typedef double k64x4 __attribute__((ext_vector_type(4)));
-
-static bool kp_dims_ok(int64_t D) { return D >= 1 && D <= KP_MAXD - 1; }
 __host__ __device__ static inline int64_t kp_tiles(int64_t n) { return (n + 15) / 16; }
 
 // ------------------------------------------------------------------------------------ standardise
@@ -46,12 +43,9 @@ __global__ void __launch_bounds__(KP_STD_NT) kp_prepare_kernel(const double* __r
                                                                const double* __restrict__ mean,
                                                                const double* __restrict__ scale, double* z,
                                                                double* nrm) {
-    __shared__ double sm[KP_MAXD], si[KP_MAXD];
+    __shared__ double sm[FOLD_MAXD], si[FOLD_MAXD];
     const int tid = threadIdx.x;
-    if (tid < D) {
-        sm[tid] = mean[tid];
-        si[tid] = 1.0 / scale[tid];
-    }
+    stage_scaler(sm, si, mean, scale, 0, D);
     __syncthreads();
     const int sub = tid & 15;
     const int64_t r = (int64_t)blockIdx.x * 64 + (tid >> 4);
@@ -61,15 +55,12 @@ __global__ void __launch_bounds__(KP_STD_NT) kp_prepare_kernel(const double* __r
         const double* src = x + r * D;
         double* dst = z + r * D;
         for (int k = sub; k < D; k += 16) {
-            const double v = (src[k] - sm[k]) * si[k];
+            const double v = zscore(src[k], sm[k], si[k]);
             dst[k] = v;
             acc += v * v;
         }
     }
-    acc += __shfl_xor(acc, 8, 16);
-    acc += __shfl_xor(acc, 4, 16);
-    acc += __shfl_xor(acc, 2, 16);
-    acc += __shfl_xor(acc, 1, 16);
+    acc = lane16_sum(acc);
     if (ok && sub == 0) nrm[r] = acc;
 }
 
@@ -84,20 +75,17 @@ __global__ void __launch_bounds__(KP_NT) kp_tile_kernel(const double* __restrict
                                                         const double* __restrict__ nrm,
                                                         const double* __restrict__ beta, int64_t n, double gamma,
                                                         double* __restrict__ out) {
-    __shared__ double sm[KP_MAXD], si[KP_MAXD];
+    __shared__ double sm[FOLD_MAXD], si[FOLD_MAXD];
     __shared__ double zq[16 * KP_LD];
     __shared__ double qn[16];
     const int tid = threadIdx.x;
-    for (int k = tid; k < KP_MAXD; k += KP_NT) {
-        sm[k] = k < D ? mean[k] : 0.0;
-        si[k] = k < D ? 1.0 / scale[k] : 0.0;
-    }
+    stage_scaler_padded<KP_NT>(sm, si, mean, scale, 0, D);
     __syncthreads();
     const int64_t q0 = (int64_t)blockIdx.y * 16;
-    for (int e = tid; e < 16 * KP_MAXD; e += KP_NT) {
-        const int r = e >> 8, k = e & (KP_MAXD - 1);
+    for (int e = tid; e < 16 * FOLD_MAXD; e += KP_NT) {
+        const int r = e >> 8, k = e & (FOLD_MAXD - 1);
         const int64_t q = q0 + r;
-        zq[r * KP_LD + k] = q < B && k < D ? (feat[q * D + k] - sm[k]) * si[k] : 0.0;
+        zq[r * KP_LD + k] = q < B && k < D ? zscore(feat[q * D + k], sm[k], si[k]) : 0.0;
     }
     __syncthreads();
     {
@@ -107,10 +95,7 @@ __global__ void __launch_bounds__(KP_NT) kp_tile_kernel(const double* __restrict
             const double v = zq[r * KP_LD + k];
             acc += v * v;
         }
-        acc += __shfl_xor(acc, 8, 16);
-        acc += __shfl_xor(acc, 4, 16);
-        acc += __shfl_xor(acc, 2, 16);
-        acc += __shfl_xor(acc, 1, 16);
+        acc = lane16_sum(acc);
         if (sub == 0) qn[r] = acc;
     }
     __syncthreads();
@@ -121,7 +106,7 @@ __global__ void __launch_bounds__(KP_NT) kp_tile_kernel(const double* __restrict
     const bool okb = bb < n;
     const double* rowa = zq + m * KP_LD;
     const double* rowb = z + (okb ? bb : 0) * D;
-    k64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < D; k0 += 4) {
         const int k = k0 + kk;
         const double a = rowa[k];  // zero past D and past B
@@ -134,10 +119,7 @@ __global__ void __launch_bounds__(KP_NT) kp_tile_kernel(const double* __restrict
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t q = q0 + kk + 4 * i;
-            if (q < B) {
-                const double d = (qn[kk + 4 * i] + nb) - 2.0 * acc[i];
-                out[q * n + bb] = d > 0.0 ? d : 0.0;
-            }
+            if (q < B) out[q * n + bb] = sqdist(qn[kk + 4 * i], nb, acc[i]);
         }
     } else {
         const double wb = okb ? beta[bb] : 0.0;
@@ -145,12 +127,8 @@ __global__ void __launch_bounds__(KP_NT) kp_tile_kernel(const double* __restrict
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t q = q0 + kk + 4 * i;
-            const double d = (qn[kk + 4 * i] + nb) - 2.0 * acc[i];
-            double s = okb ? wb * exp(-gamma * (d > 0.0 ? d : 0.0)) : 0.0;
-            s += __shfl_xor(s, 8, 16);
-            s += __shfl_xor(s, 4, 16);
-            s += __shfl_xor(s, 2, 16);
-            s += __shfl_xor(s, 1, 16);
+            const double d = sqdist(qn[kk + 4 * i], nb, acc[i]);
+            const double s = lane16_sum(okb ? wb * exp(-gamma * d) : 0.0);
             if (m == 0 && q < B) out[q * tiles + tile] = s;
         }
     }
@@ -290,14 +268,14 @@ static int64_t kp_ws_bytes(int64_t n, int64_t B, int kind) {
 using namespace edgedet;
 
 extern "C" int64_t edgedet_kmodel_workspace_size(int64_t n, int64_t D, int64_t B, int32_t kind) {
-    if (!kp_dims_ok(D) || B < 1 || B > KP_MAXB || n > KP_MAXN) return -1;
+    if (!fold_dims_ok(D) || B < 1 || B > KP_MAXB || n > KP_MAXN) return -1;
     if (kind == KIND_SVR ? n < 0 : (kind != KIND_KNR || n < 1)) return -1;
     return kp_ws_bytes(n, B, kind);
 }
 
 extern "C" int edgedet_kmodel_prepare(const double* rows, int64_t n, int64_t D, const double* mean,
                                       const double* scale, double* z, double* norm, void* stream) {
-    EDGEDET_REQUIRE(kp_dims_ok(D) && n >= 0 && n <= KP_MAXN, "kmodel_prepare: 1 <= features <= 255, 0 <= rows <= 2^30");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && n >= 0 && n <= KP_MAXN, "kmodel_prepare: 1 <= features <= 255, 0 <= rows <= 2^30");
     EDGEDET_REQUIRE(mean && scale && (n == 0 || (rows && z && norm)), "kmodel_prepare: null pointer");
     if (n == 0) return 0;
     hipLaunchKernelGGL(kp_prepare_kernel, dim3((unsigned)cdiv(n, 64)), dim3(KP_STD_NT), 0, (hipStream_t)stream, rows, n,
@@ -310,7 +288,7 @@ extern "C" int edgedet_svr_model_predict(const double* feat, int64_t B, int64_t 
                                          const double* scale, const double* z, const double* norm,
                                          const double* beta, int64_t n, double gamma, double intercept, void* ws,
                                          int64_t ws_bytes, double* est, void* stream) {
-    EDGEDET_REQUIRE(kp_dims_ok(D) && B >= 1 && B <= KP_MAXB && n >= 0 && n <= KP_MAXN,
+    EDGEDET_REQUIRE(fold_dims_ok(D) && B >= 1 && B <= KP_MAXB && n >= 0 && n <= KP_MAXN,
                     "svr_model_predict: 1 <= features <= 255, 1 <= rows <= 1,048,560, 0 <= support vectors <= 2^30");
     EDGEDET_REQUIRE(feat && mean && scale && ws && est && (n == 0 || (z && norm && beta)),
                     "svr_model_predict: null pointer");
@@ -332,7 +310,7 @@ extern "C" int edgedet_knn_model_predict(const double* feat, int64_t B, int64_t 
                                          const double* scale, const double* z, const double* norm,
                                          const double* target, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
                                          double* est, int32_t* nbr, void* stream) {
-    EDGEDET_REQUIRE(kp_dims_ok(D) && B >= 1 && B <= KP_MAXB && n >= 1 && n <= KP_MAXN,
+    EDGEDET_REQUIRE(fold_dims_ok(D) && B >= 1 && B <= KP_MAXB && n >= 1 && n <= KP_MAXN,
                     "knn_model_predict: 1 <= features <= 255, 1 <= rows <= 1,048,560, 1 <= training rows <= 2^30");
     EDGEDET_REQUIRE(k >= 1 && k <= n, "knn_model_predict: 1 <= n_neighbors <= training rows");
     EDGEDET_REQUIRE(feat && mean && scale && z && norm && target && ws && est, "knn_model_predict: null pointer");

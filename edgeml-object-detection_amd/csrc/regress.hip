@@ -1,6 +1,7 @@
 // regression.py's deterministic sklearn estimators on the device, every cross-validation fold in flight:
 // LinearRegression (LR), ElasticNet (EN), BayesianRidge (BR) and KNeighborsRegressor (KNR), each behind
-// fit_model's StandardScaler (regression.py:38-77).  Float64 throughout.
+// fit_model's StandardScaler (regression.py:38-77).  Float64 throughout; the steps shared with the other
+// estimator files (zscore, sqdist, lane16_sum, block_sum / block_max, fold_row) are fold_math.hpp's.
 //
 //   reg_scaler_kernel  one workgroup per fold: mean, population variance and scale = sqrt(var) of every
 //                      column over the fold's training rows (constant columns take scale 1 by sklearn's
@@ -24,47 +25,16 @@
 //                      training position) and the mean of the k targets summed in position order.
 #include <vector>
 
+#include "fold_math.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
 
 constexpr int REG_NT = 1024;
-constexpr int REG_MAXD = 256;  // padded width (features + target column)
 constexpr double REG_EPS = 2.220446049250313e-16;
 
-typedef double r64x4 __attribute__((ext_vector_type(4)));
-
-static bool reg_dims_ok(int64_t D) { return D >= 1 && D <= REG_MAXD - 1; }
 static int64_t reg_dp(int64_t D) { return (D + 1 + 15) / 16 * 16; }
 static int64_t reg_de(int64_t D) { return (D + 1) / 2 * 2; }  // Jacobi order: D rounded up to even
-
-template <int NT>
-__device__ __forceinline__ double reg_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-template <int NT>
-__device__ __forceinline__ double reg_block_max(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    return red[0];
-}
-
-__device__ __forceinline__ int64_t reg_row(const int32_t* idx, int64_t t0, int64_t r) {
-    return idx ? (int64_t)idx[t0 + r] : t0 + r;
-}
 
 // --------------------------------------------------------------------------------------- scaler
 // A column per thread (tid & 255), four row groups (tid >> 8) summed in a fixed order.
@@ -78,9 +48,9 @@ __global__ void __launch_bounds__(REG_NT) reg_scaler_kernel(const double* __rest
     const int64_t t0 = tr_off[fold], n = tr_off[fold + 1] - t0;
     double acc = 0.0;
     if (col < D)
-        for (int64_t r = rg; r < n; r += 4) acc += x[reg_row(tr_idx, t0, r) * D + col];
+        for (int64_t r = rg; r < n; r += 4) acc += x[fold_row(tr_idx, t0, r) * D + col];
     else if (col == D && y)
-        for (int64_t r = rg; r < n; r += 4) acc += y[(int64_t)fold * N + reg_row(tr_idx, t0, r)];
+        for (int64_t r = rg; r < n; r += 4) acc += y[(int64_t)fold * N + fold_row(tr_idx, t0, r)];
     red[tid] = acc;
     __syncthreads();
     const double mu = (((red[col] + red[256 + col]) + red[512 + col]) + red[768 + col]) / (double)n;
@@ -88,7 +58,7 @@ __global__ void __launch_bounds__(REG_NT) reg_scaler_kernel(const double* __rest
     acc = 0.0;
     if (col < D)
         for (int64_t r = rg; r < n; r += 4) {
-            const double d = x[reg_row(tr_idx, t0, r) * D + col] - mu;
+            const double d = x[fold_row(tr_idx, t0, r) * D + col] - mu;
             acc += d * d;
         }
     red[tid] = acc;
@@ -129,7 +99,7 @@ __global__ void __launch_bounds__(256) reg_gram_kernel(const double* __restrict_
     const double ia = ca < D ? 1.0 / scale[(int64_t)fold * D + ca] : 1.0;
     const double ib = cb < D ? 1.0 / scale[(int64_t)fold * D + cb] : 1.0;
     const bool ya = ca == D && y, yb = cb == D && y;
-    r64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     constexpr int U = 4;  // k-steps whose loads are in flight together
     for (int64_t r0 = 4 * (int64_t)wave; r0 < n; r0 += 16 * U) {
         double a[U], b[U];
@@ -139,13 +109,13 @@ __global__ void __launch_bounds__(256) reg_gram_kernel(const double* __restrict_
             a[u] = 0.0;
             b[u] = 0.0;
             if (r < n) {
-                const int64_t row = reg_row(tr_idx, t0, r);
+                const int64_t row = fold_row(tr_idx, t0, r);
                 if (ca < D)
-                    a[u] = (x[row * D + ca] - ma) * ia;
+                    a[u] = zscore(x[row * D + ca], ma, ia);
                 else if (ya)
                     a[u] = y[(int64_t)fold * N + row] - ma;
                 if (cb < D)
-                    b[u] = (x[row * D + cb] - mb) * ib;
+                    b[u] = zscore(x[row * D + cb], mb, ib);
                 else if (yb)
                     b[u] = y[(int64_t)fold * N + row] - mb;
             }
@@ -177,8 +147,8 @@ struct EighParams {
 
 __global__ void __launch_bounds__(REG_NT) reg_eigh_kernel(EighParams p) {
     __shared__ double red[REG_NT];
-    __shared__ double sc[REG_MAXD / 2], ss[REG_MAXD / 2];
-    __shared__ int sp[REG_MAXD / 2], sq[REG_MAXD / 2];
+    __shared__ double sc[FOLD_MAXD / 2], ss[FOLD_MAXD / 2];
+    __shared__ int sp[FOLD_MAXD / 2], sq[FOLD_MAXD / 2];
     const int fold = blockIdx.x, tid = threadIdx.x, D = p.D, De = p.De, np = De / 2, n1 = De - 1;
     const double* G = p.G + (int64_t)fold * p.Dp * p.Dp;
     double* A = p.A + (int64_t)fold * De * De;
@@ -191,7 +161,7 @@ __global__ void __launch_bounds__(REG_NT) reg_eigh_kernel(EighParams p) {
         fro += g * g;
     }
     for (int e = tid; e < D * D; e += REG_NT) Vt[e] = (e / D == e % D) ? 1.0 : 0.0;
-    fro = sqrt(reg_block_sum<REG_NT>(fro, red));
+    fro = sqrt(block_sum<REG_NT>(fro, red));
     const double thresh = (double)D * REG_EPS * fro;
     int sweep = 0;
     double off = 0.0;
@@ -203,7 +173,7 @@ __global__ void __launch_bounds__(REG_NT) reg_eigh_kernel(EighParams p) {
             const double a = A[e];
             o += i != j ? a * a : 0.0;
         }
-        off = sqrt(reg_block_sum<REG_NT>(o, red));
+        off = sqrt(block_sum<REG_NT>(o, red));
         conv = off <= thresh;
         if (conv || sweep >= p.max_sweeps) break;  // uniform
         for (int r = 0; r < n1; ++r) {
@@ -289,13 +259,13 @@ __global__ void __launch_bounds__(256) reg_lr_kernel(const double* __restrict__ 
                                                      const double* __restrict__ lam,
                                                      const double* __restrict__ vt, double tau, double* coef,
                                                      int32_t* rank, double* min_ratio) {
-    __shared__ double red[256], sq[REG_MAXD], st[REG_MAXD];
+    __shared__ double red[256], sq[FOLD_MAXD], st[FOLD_MAXD];
     const int fold = blockIdx.x, tid = threadIdx.x;
     const double* Gf = G + (int64_t)fold * Dp * Dp;
     const double* Vt = vt + (int64_t)fold * D * D;
     const double l = tid < D ? lam[(int64_t)fold * D + tid] : 0.0;
     if (tid < D) sq[tid] = Gf[(int64_t)tid * Dp + D];
-    const double lmax = reg_block_max<256>(l, red);  // its barriers order the sq stores
+    const double lmax = block_max<256>(l, red);  // its barriers order the sq stores
     const bool keep = tid < D && lmax > 0.0 && l > tau * lmax;
     double t = 0.0;
     if (keep) {
@@ -304,8 +274,8 @@ __global__ void __launch_bounds__(256) reg_lr_kernel(const double* __restrict__ 
         t = pi / l;
     }
     st[tid] = t;
-    const double nkeep = reg_block_sum<256>(keep ? 1.0 : 0.0, red);  // also orders the st stores
-    const double rmin = -reg_block_max<256>(keep ? -(l / lmax) : -1.0, red);
+    const double nkeep = block_sum<256>(keep ? 1.0 : 0.0, red);  // also orders the st stores
+    const double rmin = -block_max<256>(keep ? -(l / lmax) : -1.0, red);
     if (tid < D) {
         double c = 0.0;
         for (int i = 0; i < D; ++i) c += Vt[(int64_t)i * D + tid] * st[i];
@@ -333,7 +303,7 @@ struct BrParams {
 };
 
 __global__ void __launch_bounds__(256) reg_br_kernel(BrParams p) {
-    __shared__ double red[256], sq[REG_MAXD], sc[REG_MAXD];
+    __shared__ double red[256], sq[FOLD_MAXD], sc[FOLD_MAXD];
     const int fold = blockIdx.x, tid = threadIdx.x, D = p.D;
     const double* Gf = p.G + (int64_t)fold * p.Dp * p.Dp;
     const double* Vt = p.vt + (int64_t)fold * D * D;
@@ -356,14 +326,14 @@ __global__ void __launch_bounds__(256) reg_br_kernel(BrParams p) {
         coef = 0.0;
         if (tid < D)
             for (int i = 0; i < D; ++i) coef += Vt[(int64_t)i * D + tid] * sc[i];
-        const double cp = reg_block_sum<256>(ci * pi, red);
-        const double lcc = reg_block_sum<256>(l * ci * ci, red);
+        const double cp = block_sum<256>(ci * pi, red);
+        const double lcc = block_sum<256>(l * ci * ci, red);
         const double sse = (yy - 2.0 * cp) + lcc;
-        const double gamma = reg_block_sum<256>(tid < D ? (alpha * l) / (lambda + alpha * l) : 0.0, red);
-        const double c2 = reg_block_sum<256>(coef * coef, red);
+        const double gamma = block_sum<256>(tid < D ? (alpha * l) / (lambda + alpha * l) : 0.0, red);
+        const double c2 = block_sum<256>(coef * coef, red);
         lambda = (gamma + 2.0 * p.lambda_1) / (c2 + 2.0 * p.lambda_2);
         alpha = (n - gamma + 2.0 * p.alpha_1) / (sse + 2.0 * p.alpha_2);
-        const double dc = reg_block_sum<256>(fabs(coef_old - coef), red);
+        const double dc = block_sum<256>(fabs(coef_old - coef), red);
         if (iter != 0 && dc < p.tol) break;  // uniform
         coef_old = coef;
     }
@@ -401,13 +371,13 @@ struct EnParams {
 };
 
 __global__ void __launch_bounds__(256) reg_en_kernel(EnParams p) {
-    __shared__ double red[256], sw[REG_MAXD], sh[REG_MAXD];
+    __shared__ double red[256], sw[FOLD_MAXD], sh[FOLD_MAXD];
     const int fold = blockIdx.x, tid = threadIdx.x, D = p.D, Dp = p.Dp;
     const double* Gf = p.G + (int64_t)fold * Dp * Dp;
     const double inv_n = 1.0 / (double)(p.tr_off[fold + 1] - p.tr_off[fold]);
     const double l1 = p.alpha * p.l1_ratio, l2 = p.alpha * (1.0 - p.l1_ratio);
     const double qj = tid < D ? Gf[(int64_t)tid * Dp + D] * inv_n : 0.0;
-    const double tol = p.tol_abs > 0.0 ? p.tol_abs : p.tol_rel * reg_block_max<256>(fabs(qj), red);
+    const double tol = p.tol_abs > 0.0 ? p.tol_abs : p.tol_rel * block_max<256>(fabs(qj), red);
     sw[tid] = 0.0;
     sh[tid] = -qj;
     __syncthreads();
@@ -422,7 +392,7 @@ __global__ void __launch_bounds__(256) reg_en_kernel(EnParams p) {
                 const double w = sw[tid], g = sh[tid] + l2 * w;
                 z = w != 0.0 ? g + (w > 0.0 ? l1 : -l1) : fmax(fabs(g) - l1, 0.0);
             }
-            zn = sqrt(reg_block_sum<256>(z * z, red));
+            zn = sqrt(block_sum<256>(z * z, red));
             conv = zn <= tol;
             if (!conv || pass == 1) break;  // uniform
             double h = 0.0;
@@ -468,7 +438,7 @@ __global__ void __launch_bounds__(REG_NT) reg_predict_kernel(const double* __res
                                                              const double* __restrict__ scale,
                                                              const double* __restrict__ coef,
                                                              const double* __restrict__ ymean, double* out) {
-    __shared__ double sm[REG_MAXD], sv[REG_MAXD];
+    __shared__ double sm[FOLD_MAXD], sv[FOLD_MAXD];
     const int fold = blockIdx.y, tid = threadIdx.x;
     if (tid < D) {
         sm[tid] = mean[(int64_t)fold * D + tid];
@@ -482,11 +452,8 @@ __global__ void __launch_bounds__(REG_NT) reg_predict_kernel(const double* __res
         const bool ok = r < N;
         double acc = 0.0;
         if (ok)
-            for (int k = sub; k < D; k += 16) acc += (x[r * D + k] - sm[k]) * sv[k];
-        acc += __shfl_xor(acc, 8, 16);
-        acc += __shfl_xor(acc, 4, 16);
-        acc += __shfl_xor(acc, 2, 16);
-        acc += __shfl_xor(acc, 1, 16);
+            for (int k = sub; k < D; k += 16) acc += zscore(x[r * D + k], sm[k], sv[k]);
+        acc = lane16_sum(acc);
         if (ok && sub == 0) out[(int64_t)fold * N + r] = acc + ymean[fold];
     }
 }
@@ -496,12 +463,9 @@ __global__ void __launch_bounds__(REG_NT) reg_predict_kernel(const double* __res
 __global__ void __launch_bounds__(REG_NT) knn_norm_kernel(const double* __restrict__ x, int64_t N, int D,
                                                           const double* __restrict__ mean,
                                                           const double* __restrict__ scale, double* norm) {
-    __shared__ double sm[REG_MAXD], si[REG_MAXD];
+    __shared__ double sm[FOLD_MAXD], si[FOLD_MAXD];
     const int fold = blockIdx.y, tid = threadIdx.x;
-    if (tid < D) {
-        sm[tid] = mean[(int64_t)fold * D + tid];
-        si[tid] = 1.0 / scale[(int64_t)fold * D + tid];
-    }
+    stage_scaler(sm, si, mean, scale, fold, D);
     __syncthreads();
     const int sub = tid & 15, grp = tid >> 4;
     const int64_t r0 = (int64_t)blockIdx.x * REG_NT;
@@ -511,13 +475,10 @@ __global__ void __launch_bounds__(REG_NT) knn_norm_kernel(const double* __restri
         double acc = 0.0;
         if (ok)
             for (int k = sub; k < D; k += 16) {
-                const double z = (x[r * D + k] - sm[k]) * si[k];
+                const double z = zscore(x[r * D + k], sm[k], si[k]);
                 acc += z * z;
             }
-        acc += __shfl_xor(acc, 8, 16);
-        acc += __shfl_xor(acc, 4, 16);
-        acc += __shfl_xor(acc, 2, 16);
-        acc += __shfl_xor(acc, 1, 16);
+        acc = lane16_sum(acc);
         if (ok && sub == 0) norm[(int64_t)fold * N + r] = acc;
     }
 }
@@ -531,39 +492,33 @@ __global__ void __launch_bounds__(256) knn_dist_kernel(const double* __restrict_
                                                        const double* __restrict__ mean,
                                                        const double* __restrict__ scale,
                                                        const double* __restrict__ norm, double* dist) {
-    __shared__ double sm[REG_MAXD], si[REG_MAXD];
+    __shared__ double sm[FOLD_MAXD], si[FOLD_MAXD];
     const int fold = blockIdx.z, tid = threadIdx.x;
     const int64_t t0 = tr_off[fold], n = tr_off[fold + 1] - t0;
     if ((int64_t)blockIdx.x * 64 >= n) return;  // uniform: the grid covers the largest fold
-    for (int k = tid; k < REG_MAXD; k += 256) {
-        sm[k] = k < D ? mean[(int64_t)fold * D + k] : 0.0;
-        si[k] = k < D ? 1.0 / scale[(int64_t)fold * D + k] : 0.0;
-    }
+    stage_scaler_padded<256>(sm, si, mean, scale, fold, D);
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, m = lane & 15, kk = lane >> 4;
     const int64_t q0 = (int64_t)blockIdx.y * 16, b0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
     const int64_t qa = q0 + m, bb = b0 + m;
     const bool oka = qa < N, okb = bb < n;
     const double* rowa = x + (oka ? qa : 0) * D;
-    const double* rowb = x + (okb ? reg_row(tr_idx, t0, bb) : 0) * D;
-    r64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    const double* rowb = x + (okb ? fold_row(tr_idx, t0, bb) : 0) * D;
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < D; k0 += 4) {
         const int k = k0 + kk;
         const bool okk = k < D;
-        const double a = oka && okk ? (rowa[k] - sm[k]) * si[k] : 0.0;
-        const double b = okb && okk ? (rowb[k] - sm[k]) * si[k] : 0.0;
+        const double a = oka && okk ? zscore(rowa[k], sm[k], si[k]) : 0.0;
+        const double b = okb && okk ? zscore(rowb[k], sm[k], si[k]) : 0.0;
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
     }
     if (!okb) return;
-    const double nb = norm[(int64_t)fold * N + reg_row(tr_idx, t0, bb)];
+    const double nb = norm[(int64_t)fold * N + fold_row(tr_idx, t0, bb)];
     double* slab = dist + N * t0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t q = q0 + kk + 4 * i;
-        if (q < N) {
-            const double d = (norm[(int64_t)fold * N + q] + nb) - 2.0 * acc[i];
-            slab[q * n + bb] = d > 0.0 ? d : 0.0;
-        }
+        if (q < N) slab[q * n + bb] = sqdist(norm[(int64_t)fold * N + q], nb, acc[i]);
     }
 }
 
@@ -645,7 +600,7 @@ __global__ void __launch_bounds__(KNN_NT) knn_select_kernel(const double* __rest
     double acc = 0.0;
     for (int c0 = 0; c0 < k; c0 += KNN_NT) {
         const int c = c0 + tid;
-        if (c < k) sy[tid] = y[(int64_t)fold * N + reg_row(tr_idx, t0, out[c])];
+        if (c < k) sy[tid] = y[(int64_t)fold * N + fold_row(tr_idx, t0, out[c])];
         __syncthreads();
         if (tid == 0) {
             const int m = k - c0 < KNN_NT ? k - c0 : KNN_NT;
@@ -664,25 +619,16 @@ static size_t reg_ws_doubles(int64_t folds, int64_t D, int64_t N, int64_t T) {
 }
 
 extern "C" int64_t edgedet_reg_workspace_size(int32_t folds, int64_t D, int64_t N, int64_t total_rows) {
-    if (folds < 1 || !reg_dims_ok(D) || N < 0 || total_rows < 0) return -1;
+    if (folds < 1 || !fold_dims_ok(D) || N < 0 || total_rows < 0) return -1;
     return (int64_t)(reg_ws_doubles(folds, D, N, total_rows) * sizeof(double));
-}
-
-static bool reg_folds_ok(const int64_t* tr_off_host, int32_t folds, int64_t N, bool indexed) {
-    if (folds < 1 || folds > 65535 || tr_off_host[0] != 0) return false;
-    for (int f = 0; f < folds; ++f) {
-        const int64_t n = tr_off_host[f + 1] - tr_off_host[f];
-        if (n < 1 || (indexed && n > N)) return false;
-    }
-    return indexed || tr_off_host[folds] <= N;
 }
 
 extern "C" int edgedet_reg_scaler(const double* x, int64_t N, int64_t D, const double* y, const int32_t* tr_idx,
                                   const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, double* mean,
                                   double* scale, double* ymean, void* stream) {
     EDGEDET_REQUIRE(x && tr_off_host && tr_off && mean && scale && ymean, "reg_scaler: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && N >= 1, "reg_scaler: 1 <= features <= 255");
-    EDGEDET_REQUIRE(reg_folds_ok(tr_off_host, folds, N, tr_idx != nullptr), "reg_scaler: fold offsets");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1, "reg_scaler: 1 <= features <= 255");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, N, tr_idx != nullptr), "reg_scaler: fold offsets");
     hipLaunchKernelGGL(reg_scaler_kernel, dim3((unsigned)folds), dim3(REG_NT), 0, (hipStream_t)stream, x, (int)D, y, N,
                        tr_idx, tr_off, mean, scale, ymean);
     EDGEDET_LAUNCH_CHECK();
@@ -693,8 +639,8 @@ extern "C" int edgedet_reg_gram(const double* x, int64_t N, int64_t D, const dou
                                 const int64_t* tr_off_host, const int64_t* tr_off, int32_t folds, const double* mean,
                                 const double* scale, const double* ymean, double* G, void* stream) {
     EDGEDET_REQUIRE(x && tr_off_host && tr_off && mean && scale && ymean && G, "reg_gram: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && N >= 1, "reg_gram: 1 <= features <= 255");
-    EDGEDET_REQUIRE(reg_folds_ok(tr_off_host, folds, N, tr_idx != nullptr), "reg_gram: fold offsets");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1, "reg_gram: 1 <= features <= 255");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, N, tr_idx != nullptr), "reg_gram: fold offsets");
     const int Dp = (int)reg_dp(D), nt = Dp / 16;
     hipLaunchKernelGGL(reg_gram_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)folds), dim3(256), 0,
                        (hipStream_t)stream, x, (int)D, Dp, y, N, tr_idx, tr_off, mean, scale, ymean, G);
@@ -706,7 +652,7 @@ extern "C" int edgedet_reg_eigh(const double* G, int64_t D, int32_t folds, void*
                                 int32_t max_sweeps, double* lam, double* vt, int32_t* sweeps, int32_t* status,
                                 double* offnorm, void* stream) {
     EDGEDET_REQUIRE(G && ws && lam && vt && sweeps && status && offnorm, "reg_eigh: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && folds >= 1 && folds <= 65535 && max_sweeps >= 1, "reg_eigh: 1 <= order <= 255");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && folds >= 1 && folds <= 65535 && max_sweeps >= 1, "reg_eigh: 1 <= order <= 255");
     EDGEDET_REQUIRE(ws_bytes >= (int64_t)(reg_ws_doubles(folds, D, 0, 0) * sizeof(double)),
                     "reg_eigh: workspace smaller than edgedet_reg_workspace_size");
     EighParams p{};
@@ -729,7 +675,7 @@ extern "C" int edgedet_reg_eigh(const double* G, int64_t D, int32_t folds, void*
 extern "C" int edgedet_reg_fit_lr(const double* G, int64_t D, int32_t folds, const double* lam, const double* vt,
                                   double tau, double* coef, int32_t* rank, double* min_ratio, void* stream) {
     EDGEDET_REQUIRE(G && lam && vt && coef && rank && min_ratio, "reg_fit_lr: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && folds >= 1 && folds <= 65535 && tau >= 0.0, "reg_fit_lr: 1 <= features <= 255");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && folds >= 1 && folds <= 65535 && tau >= 0.0, "reg_fit_lr: 1 <= features <= 255");
     hipLaunchKernelGGL(reg_lr_kernel, dim3((unsigned)folds), dim3(256), 0, (hipStream_t)stream, G, (int)D,
                        (int)reg_dp(D), lam, vt, tau, coef, rank, min_ratio);
     EDGEDET_LAUNCH_CHECK();
@@ -741,7 +687,7 @@ extern "C" int edgedet_reg_fit_br(const double* G, int64_t D, const int64_t* tr_
                                   double lambda_1, double lambda_2, double tol, int32_t max_iter, double* coef,
                                   double* hyper, int32_t* n_iter, void* stream) {
     EDGEDET_REQUIRE(G && tr_off_host && tr_off && lam && vt && coef && hyper && n_iter, "reg_fit_br: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && folds >= 1 && folds <= 65535 && max_iter >= 1, "reg_fit_br: 1 <= features <= 255");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && folds >= 1 && folds <= 65535 && max_iter >= 1, "reg_fit_br: 1 <= features <= 255");
     for (int f = 0; f < folds; ++f)
         EDGEDET_REQUIRE(tr_off_host[f + 1] - tr_off_host[f] > D, "reg_fit_br: needs more training rows than features");
     BrParams p{};
@@ -770,7 +716,7 @@ extern "C" int edgedet_reg_fit_en(const double* G, int64_t D, const int64_t* tr_
                                   int32_t max_sweeps, double* coef, double* res, int32_t* sweeps, int32_t* status,
                                   void* stream) {
     EDGEDET_REQUIRE(G && tr_off_host && tr_off && coef && res && sweeps && status, "reg_fit_en: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && folds >= 1 && folds <= 65535 && max_sweeps >= 1, "reg_fit_en: 1 <= features <= 255");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && folds >= 1 && folds <= 65535 && max_sweeps >= 1, "reg_fit_en: 1 <= features <= 255");
     EDGEDET_REQUIRE(alpha > 0.0 && l1_ratio >= 0.0 && l1_ratio < 1.0 && (tol_abs > 0.0 || tol_rel > 0.0),
                     "reg_fit_en: alpha > 0, 0 <= l1_ratio < 1 (a strongly convex objective), a positive tolerance");
     for (int f = 0; f < folds; ++f)
@@ -798,7 +744,7 @@ extern "C" int edgedet_reg_predict(const double* x, int64_t N, int64_t D, const 
                                    const double* coef, const double* ymean, int32_t folds, double* out,
                                    void* stream) {
     EDGEDET_REQUIRE(x && mean && scale && coef && ymean && out, "reg_predict: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && N >= 1 && folds >= 1 && folds <= 65535, "reg_predict: 1 <= features <= 255");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1 && folds >= 1 && folds <= 65535, "reg_predict: 1 <= features <= 255");
     hipLaunchKernelGGL(reg_predict_kernel, dim3((unsigned)cdiv(N, REG_NT), (unsigned)folds), dim3(REG_NT), 0,
                        (hipStream_t)stream, x, N, (int)D, mean, scale, coef, ymean, out);
     EDGEDET_LAUNCH_CHECK();
@@ -811,8 +757,8 @@ extern "C" int edgedet_knn_fit_predict(const double* x, int64_t N, int64_t D, co
                                        double* est, int32_t* nbr, void* stream) {
     EDGEDET_REQUIRE(x && y && tr_idx && tr_off_host && tr_off && mean && scale && ws && est && nbr,
                     "knn_fit_predict: null pointer");
-    EDGEDET_REQUIRE(reg_dims_ok(D) && N >= 1 && N <= 65535 * 16, "knn_fit_predict: 1 <= features <= 255, rows <= 1,048,560");
-    EDGEDET_REQUIRE(reg_folds_ok(tr_off_host, folds, N, true), "knn_fit_predict: fold offsets");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1 && N <= 65535 * 16, "knn_fit_predict: 1 <= features <= 255, rows <= 1,048,560");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, N, true), "knn_fit_predict: fold offsets");
     int64_t nmax = 0;
     for (int f = 0; f < folds; ++f) {
         const int64_t n = tr_off_host[f + 1] - tr_off_host[f];

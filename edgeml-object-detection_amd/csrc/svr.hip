@@ -1,6 +1,7 @@
 // regression.py's SVR (rbf) and LinearSVR on the device, every cross-validation fold in flight, each solved
 // to a certified optimum of its strongly convex objective.  Float64 throughout, fixed-order
-// sums, no float atomics.  The standardisation is edgedet_reg_scaler's (csrc/regress.hip).
+// sums, no float atomics.  The standardisation is edgedet_reg_scaler's (csrc/regress.hip); the shared steps
+// (zscore, sqdist, lane16_sum, block_sum, the scaler's staging in LDS) are fold_math.hpp's.
 //
 //   svr_std_kernel      Z = (x - mean) * (1 / scale) of every fold's training rows into the workspace, and
 //                       |z|^2 of every row: sixteen lanes per row.
@@ -20,6 +21,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "fold_math.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
@@ -27,18 +29,9 @@ namespace edgedet {
 constexpr int SVR_NT = 1024;
 constexpr int SVR_EPT = 4;       // training rows per thread of the SMO workgroup
 constexpr int SVR_MAXN = 4000;   // training rows per fold: gradient and beta, 2 x 32,000 bytes of LDS
-constexpr int SVR_MAXD = 256;
 constexpr double SVR_TAU = 1e-12;  // libsvm's floor on a non-positive curvature
 constexpr int LSVR_NT = 256;
 constexpr int LSVR_CHECK = 10;   // sweeps between two evaluations of the duality gap
-
-typedef double s64x4 __attribute__((ext_vector_type(4)));
-
-static bool svr_dims_ok(int64_t D) { return D >= 1 && D <= SVR_MAXD - 1; }
-
-__device__ __forceinline__ int64_t svr_row(const int32_t* idx, int64_t t0, int64_t r) {
-    return idx ? (int64_t)idx[t0 + r] : t0 + r;
-}
 
 // the fold's kernel matrix starts at sum_{g < f} n_g^2
 __device__ __forceinline__ int64_t svr_koff(const int64_t* tr_off, int fold) {
@@ -50,54 +43,36 @@ __device__ __forceinline__ int64_t svr_koff(const int64_t* tr_off, int fold) {
     return o;
 }
 
-template <int NT>
-__device__ __forceinline__ double svr_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // ------------------------------------------------------------------------------------ standardise
 __global__ void __launch_bounds__(SVR_NT) svr_std_kernel(const double* __restrict__ x, int D,
                                                          const int32_t* __restrict__ tr_idx,
                                                          const int64_t* __restrict__ tr_off,
                                                          const double* __restrict__ mean,
                                                          const double* __restrict__ scale, double* z, double* nrm) {
-    __shared__ double sm[SVR_MAXD], si[SVR_MAXD];
+    __shared__ double sm[FOLD_MAXD], si[FOLD_MAXD];
     const int fold = blockIdx.y, tid = threadIdx.x;
     const int64_t t0 = tr_off[fold], n = tr_off[fold + 1] - t0;
     if ((int64_t)blockIdx.x * 64 >= n) return;  // uniform: the grid covers the largest fold
-    if (tid < D) {
-        sm[tid] = mean[(int64_t)fold * D + tid];
-        si[tid] = 1.0 / scale[(int64_t)fold * D + tid];
-    }
+    stage_scaler(sm, si, mean, scale, fold, D);
     __syncthreads();
     const int sub = tid & 15;
     const int64_t r = (int64_t)blockIdx.x * 64 + (tid >> 4);
     const bool ok = r < n;
     double acc = 0.0;
     if (ok) {
-        const double* src = x + svr_row(tr_idx, t0, r) * D;
+        const double* src = x + fold_row(tr_idx, t0, r) * D;
         double* dst = z + (t0 + r) * D;
         for (int k = sub; k < D; k += 16) {
-            const double v = (src[k] - sm[k]) * si[k];
+            const double v = zscore(src[k], sm[k], si[k]);
             dst[k] = v;
             acc += v * v;
         }
     }
-    acc += __shfl_xor(acc, 8, 16);
-    acc += __shfl_xor(acc, 4, 16);
-    acc += __shfl_xor(acc, 2, 16);
-    acc += __shfl_xor(acc, 1, 16);
+    acc = lane16_sum(acc);
     if (ok && sub == 0) nrm[t0 + r] = acc;
 }
 
-// |z|^2 of the rows of one matrix (the unit operator's norms), the same lane order as svr_std_kernel
+// |z|^2 of the rows of one matrix (the unit operator's norms): svr_std_kernel's k order, then lane16_sum
 __global__ void __launch_bounds__(SVR_NT) svr_norm_kernel(const double* __restrict__ z, int64_t n, int D,
                                                           double* nrm) {
     const int tid = threadIdx.x, sub = tid & 15;
@@ -109,10 +84,7 @@ __global__ void __launch_bounds__(SVR_NT) svr_norm_kernel(const double* __restri
             const double v = z[r * D + k];
             acc += v * v;
         }
-    acc += __shfl_xor(acc, 8, 16);
-    acc += __shfl_xor(acc, 4, 16);
-    acc += __shfl_xor(acc, 2, 16);
-    acc += __shfl_xor(acc, 1, 16);
+    acc = lane16_sum(acc);
     if (ok && sub == 0) nrm[r] = acc;
 }
 
@@ -128,13 +100,13 @@ __global__ void __launch_bounds__(SVR_NT) svr_gamma_kernel(const double* __restr
     const int64_t cnt = n * D;
     double acc = 0.0;
     for (int64_t e = tid; e < cnt; e += SVR_NT) acc += zf[e];
-    const double mu = svr_block_sum<SVR_NT>(acc, red) / (double)cnt;
+    const double mu = block_sum<SVR_NT>(acc, red) / (double)cnt;
     acc = 0.0;
     for (int64_t e = tid; e < cnt; e += SVR_NT) {
         const double d = zf[e] - mu;
         acc += d * d;
     }
-    const double var = svr_block_sum<SVR_NT>(acc, red) / (double)cnt;
+    const double var = block_sum<SVR_NT>(acc, red) / (double)cnt;
     if (tid == 0) gamma[fold] = gamma_in > 0.0 ? gamma_in : (var != 0.0 ? 1.0 / ((double)D * var) : 1.0);
 }
 
@@ -154,7 +126,7 @@ __global__ void __launch_bounds__(256) svr_kmat_kernel(const double* __restrict_
     const bool oka = qa < n, okb = bb < n;
     const double* rowa = z + (t0 + (oka ? qa : 0)) * D;
     const double* rowb = z + (t0 + (okb ? bb : 0)) * D;
-    s64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < D; k0 += 4) {
         const int k = k0 + kk;
         const bool okk = k < D;
@@ -169,8 +141,7 @@ __global__ void __launch_bounds__(256) svr_kmat_kernel(const double* __restrict_
     for (int i = 0; i < 4; ++i) {
         const int64_t q = q0 + kk + 4 * i;
         if (q < n) {
-            const double d = (nrm[t0 + q] + nb) - 2.0 * acc[i];
-            Kf[q * n + bb] = exp(-g * (d > 0.0 ? d : 0.0));
+            Kf[q * n + bb] = exp(-g * sqdist(nrm[t0 + q], nb, acc[i]));
         }
     }
 }
@@ -246,7 +217,7 @@ __global__ void __launch_bounds__(SVR_NT) svr_smo_kernel(SvrParams p) {
         yt[e] = 0.0;
         kd[e] = 1.0;
         if (t < n) {
-            yt[e] = p.y[(int64_t)fold * p.N + svr_row(p.tr_idx, t0, t)];
+            yt[e] = p.y[(int64_t)fold * p.N + fold_row(p.tr_idx, t0, t)];
             kd[e] = K[(int64_t)t * n + t];
             sB[t] = 0.0;
             sG[t] = -yt[e];
@@ -405,13 +376,10 @@ __global__ void __launch_bounds__(256) svr_predict_kernel(const double* __restri
                                                           const double* __restrict__ beta,
                                                           const double* __restrict__ intercept,
                                                           const double* __restrict__ gamma, double* out) {
-    __shared__ double sm[SVR_MAXD], si[SVR_MAXD];
+    __shared__ double sm[FOLD_MAXD], si[FOLD_MAXD];
     const int fold = blockIdx.y, tid = threadIdx.x;
     const int64_t t0 = tr_off[fold], n = tr_off[fold + 1] - t0;
-    for (int k = tid; k < SVR_MAXD; k += 256) {
-        sm[k] = k < D ? mean[(int64_t)fold * D + k] : 0.0;
-        si[k] = k < D ? 1.0 / scale[(int64_t)fold * D + k] : 0.0;
-    }
+    stage_scaler_padded<256>(sm, si, mean, scale, fold, D);
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, m = lane & 15, kk = lane >> 4;
     const int64_t q0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
@@ -421,7 +389,7 @@ __global__ void __launch_bounds__(256) svr_predict_kernel(const double* __restri
     const double* rowa = x + (oka ? qa : 0) * D;
     double qn = 0.0;
     for (int k = kk; k < D; k += 4) {
-        const double a = oka ? (rowa[k] - sm[k]) * si[k] : 0.0;
+        const double a = oka ? zscore(rowa[k], sm[k], si[k]) : 0.0;
         qn += a * a;
     }
     qn += __shfl_xor(qn, 16);
@@ -434,30 +402,23 @@ __global__ void __launch_bounds__(256) svr_predict_kernel(const double* __restri
         const int64_t bb = b0 + m;
         const bool okb = bb < n;
         const double* rowb = z + (t0 + (okb ? bb : 0)) * D;
-        s64x4 acc = {0.0, 0.0, 0.0, 0.0};
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
         for (int k0 = 0; k0 < D; k0 += 4) {
             const int k = k0 + kk;
             const bool okk = k < D;
-            const double a = oka && okk ? (rowa[k] - sm[k]) * si[k] : 0.0;
+            const double a = oka && okk ? zscore(rowa[k], sm[k], si[k]) : 0.0;
             const double b = okb && okk ? rowb[k] : 0.0;
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
         }
         const double nb = okb ? nrm[t0 + bb] : 0.0, wb = okb ? beta[t0 + bb] : 0.0;
         if (wb != 0.0) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const double d = (qi[i] + nb) - 2.0 * acc[i];
-                sum[i] += wb * exp(-g * (d > 0.0 ? d : 0.0));
-            }
+            for (int i = 0; i < 4; ++i) sum[i] += wb * exp(-g * sqdist(qi[i], nb, acc[i]));
         }
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        double s = sum[i];
-        s += __shfl_xor(s, 8, 16);
-        s += __shfl_xor(s, 4, 16);
-        s += __shfl_xor(s, 2, 16);
-        s += __shfl_xor(s, 1, 16);
+        const double s = lane16_sum(sum[i]);
         const int64_t q = q0 + kk + 4 * i;
         if (m == 0 && q < N) out[(int64_t)fold * N + q] = s + intercept[fold];
     }
@@ -498,7 +459,7 @@ __device__ double lsvr_gap(const LsvrParams& p, const double* zf, const double* 
         sv[tid] = acc;
     }
     __syncthreads();
-    const double vv = svr_block_sum<LSVR_NT>(tid < Dt ? sv[tid] * sv[tid] : 0.0, red);
+    const double vv = block_sum<LSVR_NT>(tid < Dt ? sv[tid] * sv[tid] : 0.0, red);
     const int sub = tid & 15, grp = tid >> 4;
     double hinge = 0.0, yb = 0.0, l1 = 0.0;
     for (int i0 = 0; i0 < n; i0 += LSVR_NT / 16) {
@@ -507,25 +468,22 @@ __device__ double lsvr_gap(const LsvrParams& p, const double* zf, const double* 
         double dot = 0.0;
         if (ok)
             for (int k = sub; k < Dt; k += 16) dot += (k < D ? zf[(int64_t)i * D + k] : 1.0) * sv[k];
-        dot += __shfl_xor(dot, 8, 16);
-        dot += __shfl_xor(dot, 4, 16);
-        dot += __shfl_xor(dot, 2, 16);
-        dot += __shfl_xor(dot, 1, 16);
+        dot = lane16_sum(dot);
         if (ok && sub == 0) {
-            const double yi = yf[svr_row(p.tr_idx, t0, i)], b = bf[i];
+            const double yi = yf[fold_row(p.tr_idx, t0, i)], b = bf[i];
             hinge += fmax(fabs(yi - dot) - p.eps, 0.0);
             yb += yi * b;
             l1 += fabs(b);
         }
     }
-    hinge = svr_block_sum<LSVR_NT>(hinge, red);
-    yb = svr_block_sum<LSVR_NT>(yb, red);
-    l1 = svr_block_sum<LSVR_NT>(l1, red);
+    hinge = block_sum<LSVR_NT>(hinge, red);
+    yb = block_sum<LSVR_NT>(yb, red);
+    l1 = block_sum<LSVR_NT>(l1, red);
     return ((vv + p.C * hinge) - yb) + p.eps * l1;
 }
 
 __global__ void __launch_bounds__(LSVR_NT) lsvr_fit_kernel(LsvrParams p) {
-    __shared__ double sv[SVR_MAXD], red[LSVR_NT], part[4][256], sM[256], dpart[4][4][16], sg[16], sd[16];
+    __shared__ double sv[FOLD_MAXD], red[LSVR_NT], part[4][256], sM[256], dpart[4][4][16], sg[16], sd[16];
     const int fold = blockIdx.x, tid = threadIdx.x, D = p.D, Dt = D + 1;
     const int64_t t0 = p.tr_off[fold];
     const int n = (int)(p.tr_off[fold + 1] - t0);
@@ -536,9 +494,9 @@ __global__ void __launch_bounds__(LSVR_NT) lsvr_fit_kernel(LsvrParams p) {
     double p0 = 0.0;
     for (int i = tid; i < n; i += LSVR_NT) {
         bf[i] = 0.0;
-        p0 += fmax(fabs(yf[svr_row(p.tr_idx, t0, i)]) - p.eps, 0.0);
+        p0 += fmax(fabs(yf[fold_row(p.tr_idx, t0, i)]) - p.eps, 0.0);
     }
-    p0 = p.C * svr_block_sum<LSVR_NT>(p0, red);
+    p0 = p.C * block_sum<LSVR_NT>(p0, red);
     const double tol = p.tol_abs > 0.0 ? p.tol_abs : p.tol_rel * p0;
     int sweep = 0;
     bool conv = false;
@@ -553,16 +511,16 @@ __global__ void __launch_bounds__(LSVR_NT) lsvr_fit_kernel(LsvrParams p) {
             const int r = i0 + m;
             const bool ok = r < n;
             const double* zr = zf + (int64_t)(ok ? r : 0) * D;
-            s64x4 acc = {0.0, 0.0, 0.0, 0.0};
+            f64x4 acc = {0.0, 0.0, 0.0, 0.0};
             double dot = 0.0;
-            double xs[SVR_MAXD / 16];  // every load in flight before the first matrix instruction
+            double xs[FOLD_MAXD / 16];  // every load in flight before the first matrix instruction
 #pragma unroll
-            for (int u = 0; u < SVR_MAXD / 16; ++u) {
+            for (int u = 0; u < FOLD_MAXD / 16; ++u) {
                 const int k = 4 * wave + 16 * u + kk;
                 xs[u] = ok ? (k < D ? zr[k] : (k == D ? 1.0 : 0.0)) : 0.0;
             }
 #pragma unroll
-            for (int u = 0; u < SVR_MAXD / 16; ++u) {
+            for (int u = 0; u < FOLD_MAXD / 16; ++u) {
                 const int k0 = 4 * wave + 16 * u, k = k0 + kk;
                 if (k0 < Dt) {  // uniform per wave
                     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xs[u], xs[u], acc, 0, 0, 0);
@@ -578,7 +536,7 @@ __global__ void __launch_bounds__(LSVR_NT) lsvr_fit_kernel(LsvrParams p) {
                 double g = 0.0;
                 for (int w = 0; w < 4; ++w)
                     for (int q = 0; q < 4; ++q) g += dpart[w][q][tid];
-                sg[tid] = i0 + tid < n ? g - yf[svr_row(p.tr_idx, t0, i0 + tid)] : 0.0;
+                sg[tid] = i0 + tid < n ? g - yf[fold_row(p.tr_idx, t0, i0 + tid)] : 0.0;
             }
             __syncthreads();
             if (wave == 0) {  // every group of sixteen lanes runs the same sixteen updates; the first stores
@@ -636,15 +594,6 @@ __global__ void __launch_bounds__(LSVR_NT) lsvr_fit_kernel(LsvrParams p) {
 }
 
 // ------------------------------------------------------------------------------------- the C-ABI
-static bool svr_folds_ok(const int64_t* tr_off_host, int32_t folds, int64_t N) {
-    if (!tr_off_host || folds < 1 || folds > 65535 || tr_off_host[0] != 0) return false;
-    for (int f = 0; f < folds; ++f) {
-        const int64_t n = tr_off_host[f + 1] - tr_off_host[f];
-        if (n < 1 || (N > 0 && n > N)) return false;
-    }
-    return true;
-}
-
 static int64_t svr_ws_doubles(const int64_t* tr_off_host, int32_t folds, int64_t D, bool with_kernel) {
     const int64_t T = tr_off_host[folds];
     int64_t k = 0;
@@ -657,14 +606,14 @@ static int64_t svr_ws_doubles(const int64_t* tr_off_host, int32_t folds, int64_t
 
 extern "C" int64_t edgedet_svr_workspace_size(const int64_t* tr_off_host, int32_t folds, int64_t D,
                                               int32_t with_kernel) {
-    if (!svr_dims_ok(D) || !svr_folds_ok(tr_off_host, folds, 0)) return -1;
+    if (!fold_dims_ok(D) || !folds_ok(tr_off_host, folds, 0, true)) return -1;
     return svr_ws_doubles(tr_off_host, folds, D, with_kernel != 0) * (int64_t)sizeof(double);
 }
 
 extern "C" int edgedet_svr_kernel_matrix(const double* z, int64_t n, int64_t D, double gamma_in, double* norm,
                                          double* gamma, double* K, void* stream) {
     EDGEDET_REQUIRE(z && norm && gamma && K, "svr_kernel_matrix: null pointer");
-    EDGEDET_REQUIRE(svr_dims_ok(D) && n >= 1 && n <= 65535 * 16, "svr_kernel_matrix: 1 <= features <= 255, 1 <= rows");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && n >= 1 && n <= 65535 * 16, "svr_kernel_matrix: 1 <= features <= 255, 1 <= rows");
     EDGEDET_REQUIRE(gamma_in >= 0.0, "svr_kernel_matrix: gamma > 0, or 0 for gamma='scale'");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(svr_norm_kernel, dim3((unsigned)cdiv(n, 64)), dim3(SVR_NT), 0, st, z, n, (int)D, norm);
@@ -699,8 +648,8 @@ extern "C" int edgedet_svr_fit(const double* x, int64_t N, int64_t D, const doub
     EDGEDET_REQUIRE(x && y && tr_idx && tr_off_host && tr_off && mean && scale && ws && beta && intercept && gamma &&
                         viol && iters && status,
                     "svr_fit: null pointer");
-    EDGEDET_REQUIRE(svr_dims_ok(D) && N >= 1, "svr_fit: 1 <= features <= 255");
-    EDGEDET_REQUIRE(svr_folds_ok(tr_off_host, folds, N), "svr_fit: fold offsets (every fold non-empty)");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1, "svr_fit: 1 <= features <= 255");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, N, true), "svr_fit: fold offsets (every fold non-empty)");
     EDGEDET_REQUIRE(C > 0.0 && epsilon >= 0.0 && tol > 0.0 && max_iter >= 1,
                     "svr_fit: C > 0, epsilon >= 0, tol > 0, max_iter >= 1");
     EDGEDET_REQUIRE(((uintptr_t)ws & 7) == 0, "svr_fit: the workspace is not 8-byte aligned");
@@ -747,8 +696,8 @@ extern "C" int edgedet_svr_predict(const double* x, int64_t N, int64_t D, const 
                                    double* out, void* stream) {
     EDGEDET_REQUIRE(x && mean && scale && tr_off_host && tr_off && ws && beta && intercept && gamma && out,
                     "svr_predict: null pointer");
-    EDGEDET_REQUIRE(svr_dims_ok(D) && N >= 1 && N <= (int64_t)INT_MAX * 64, "svr_predict: 1 <= features <= 255");
-    EDGEDET_REQUIRE(svr_folds_ok(tr_off_host, folds, 0), "svr_predict: fold offsets (every fold non-empty)");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1 && N <= (int64_t)INT_MAX * 64, "svr_predict: 1 <= features <= 255");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, 0, true), "svr_predict: fold offsets (every fold non-empty)");
     EDGEDET_REQUIRE(((uintptr_t)ws & 7) == 0, "svr_predict: the workspace is not 8-byte aligned");
     EDGEDET_REQUIRE(ws_bytes >= svr_ws_doubles(tr_off_host, folds, D, false) * (int64_t)sizeof(double),
                     "svr_predict: workspace smaller than edgedet_svr_workspace_size");
@@ -768,8 +717,8 @@ extern "C" int edgedet_lsvr_fit(const double* x, int64_t N, int64_t D, const dou
     EDGEDET_REQUIRE(x && y && tr_idx && tr_off_host && tr_off && mean && scale && ws && beta && v && res && sweeps &&
                         status,
                     "lsvr_fit: null pointer");
-    EDGEDET_REQUIRE(svr_dims_ok(D) && N >= 1, "lsvr_fit: 1 <= features <= 255");
-    EDGEDET_REQUIRE(svr_folds_ok(tr_off_host, folds, N), "lsvr_fit: fold offsets (every fold non-empty)");
+    EDGEDET_REQUIRE(fold_dims_ok(D) && N >= 1, "lsvr_fit: 1 <= features <= 255");
+    EDGEDET_REQUIRE(folds_ok(tr_off_host, folds, N, true), "lsvr_fit: fold offsets (every fold non-empty)");
     EDGEDET_REQUIRE(tr_off_host[folds] <= INT_MAX, "lsvr_fit: too many training rows");
     EDGEDET_REQUIRE(C > 0.0 && epsilon >= 0.0 && (tol_abs > 0.0 || tol_rel > 0.0) && max_sweeps >= 1,
                     "lsvr_fit: C > 0, epsilon >= 0, a positive tolerance, max_sweeps >= 1");

@@ -29,7 +29,8 @@ stream (tests/test_gpu_estimator.py).
 KNeighborsRegressor (behind fit_model's StandardScaler, float64) through edgeml_amd.regress
 (csrc/regress.hip): estimate<k>.npz goes to <save_dir> itself (regression.py:447-448) and,
 with --model-dir, wts<k>.pickle holds plain numpy data instead of sklearn objects.  SVR and LSVR have a
-module and CLI of their own, edgeml_amd.svr, and so has GBR, edgeml_amd.gbr (§6e).  SGD, RFR
+module and CLI of their own, edgeml_amd.svr, and so has GBR, edgeml_amd.gbr (§6e); what the
+three CLIs share lives here: base_parser, load_inputs, fold_targets, report_folds.  SGD, RFR
 (random streams) and the hidden-layer feature maps of the external YOLOv5 (stages 0-23) are out of scope
 (DESIGN.md §7); this CLI exits naming what it builds.
 """
@@ -263,10 +264,36 @@ def fold_targets(reward, split, normalize, dtype):
     return y
 
 
-def main_regressor(opts, features, reward, split):
-    """--model LR | EN | BR | KNR (regression.py:80-117, 214-217, 447-448): estimate{k}.npz in save_dir itself
-    and, with --model-dir, wts{k}.pickle holding plain numpy data (not the reference's sklearn objects)."""
+def load_inputs(opts):
+    """The three inputs of every regression CLI (regression.py:399-407): stage-24 features, reward, split."""
+    features = load_stage24(opts.data_dir)
+    with np.load(opts.reward_path, allow_pickle=False) as z:
+        reward = z["reward"]
+    assert len(features) == len(reward), "Inconsistent number of feature maps and offloading rewards."
+    split = np.load(opts.split_path, allow_pickle=False)
+    assert len(reward) == split.shape[1], "Inconsistent number of data points from the dataset and the split."
+    return features, reward, split
+
+
+def report_folds(opts, name, y, split, results, fold_model):
+    """What every sklearn-model CLI does per fold (regression.py:72, 447-448): fit_model's MSE line,
+    estimate{k}.npz in save_dir itself and, with --model-dir, wts{k}.pickle holding fold_model(k): plain numpy
+    data, not the reference's sklearn objects."""
     import pickle
+    for cv_idx, val_mask in enumerate(split):
+        r = results[cv_idx]
+        tr_mse = float(np.mean((y[cv_idx, ~val_mask] - r["train_est"]) ** 2))
+        va_mse = float(np.mean((y[cv_idx, val_mask] - r["val_est"]) ** 2)) if val_mask.any() else float("nan")
+        print(f"fold {cv_idx + 1}: Trained {name} model with training MSE: {tr_mse:.3f}, validation MSE: {va_mse:.3f}")
+        save_result(opts.save_dir, r, cv_idx)
+        if opts.model_dir != "":
+            Path(opts.model_dir).mkdir(parents=True, exist_ok=True)
+            with open(os.path.join(opts.model_dir, f"wts{cv_idx + 1}.pickle"), "wb") as f:
+                pickle.dump(fold_model(cv_idx), f)
+
+
+def main_regressor(opts, features, reward, split):
+    """--model LR | EN | BR | KNR (regression.py:80-117, 214-217)."""
     import sys
 
     from . import regress
@@ -277,29 +304,15 @@ def main_regressor(opts, features, reward, split):
             if r < regress.LR_WARN_RATIO:
                 print(f"warning: fold {f + 1}: the smallest kept eigenvalue of Z^T Z is {r:.3e} of the largest "
                       f"(rank {info['rank'][f]}): the least-squares solution is ill-conditioned", file=sys.stderr)
-    for cv_idx, val_mask in enumerate(split):
-        r = results[cv_idx]
-        tr_mse = float(np.mean((y[cv_idx, ~val_mask] - r["train_est"]) ** 2))
-        va_mse = float(np.mean((y[cv_idx, val_mask] - r["val_est"]) ** 2)) if val_mask.any() else float("nan")
-        print(f"fold {cv_idx + 1}: Trained {regress.NAMES[opts.model]} model with training MSE: {tr_mse:.3f}, "
-              f"validation MSE: {va_mse:.3f}")
-        save_result(opts.save_dir, r, cv_idx)
-        if opts.model_dir != "":
-            Path(opts.model_dir).mkdir(parents=True, exist_ok=True)
-            with open(os.path.join(opts.model_dir, f"wts{cv_idx + 1}.pickle"), "wb") as f:
-                rows = (features, y) if opts.model == "KNR" else ()  # a KNR model is its training set
-                pickle.dump(regress.model_data(opts.model, info, cv_idx, *rows), f)
+    rows = (features, y) if opts.model == "KNR" else ()  # a KNR model is its training set
+    report_folds(opts, regress.NAMES[opts.model], y, split, results,
+                 lambda fold: regress.model_data(opts.model, info, fold, *rows))
     return results, info
 
 
 def main(opts):
     check_model(opts)
-    features = load_stage24(opts.data_dir)
-    with np.load(opts.reward_path, allow_pickle=False) as z:
-        reward = z["reward"]
-    assert len(features) == len(reward), "Inconsistent number of feature maps and offloading rewards."
-    split = np.load(opts.split_path, allow_pickle=False)
-    assert len(reward) == split.shape[1], "Inconsistent number of data points from the dataset and the split."
+    features, reward, split = load_inputs(opts)
     if opts.model in REGRESSORS:
         return main_regressor(opts, features, reward, split)
     cnn = CNNOpt(weight=opts.weight and opts.normalize)
@@ -327,8 +340,9 @@ def save_state(path, spec, state, index):
     torch.save(named, os.path.join(path, f"wts{index + 1}.pth"))
 
 
-def getargs(argv=None):
-    a = argparse.ArgumentParser()
+def base_parser(model, prog=None):
+    """regression.py's own arguments (regression.py:455-480), `model` the default of --model; each CLI adds its own."""
+    a = argparse.ArgumentParser(prog=prog)
     a.add_argument("data_dir")
     a.add_argument("reward_path")
     a.add_argument("split_path")
@@ -337,8 +351,13 @@ def getargs(argv=None):
     a.add_argument("--weight", action="store_true")
     a.add_argument("--stage", type=int, default=24)
     a.add_argument("--resize", type=int, default=0)
-    a.add_argument("--model", type=str, default="CNN")
+    a.add_argument("--model", type=str, default=model)
     a.add_argument("--model-dir", type=str, default="")
+    return a
+
+
+def getargs(argv=None):
+    a = base_parser("CNN")
     a.add_argument("--seed", type=int, default=0)
     return a.parse_args(argv)
 

@@ -25,19 +25,16 @@ with --model-dir, wts<k>.pickle holding plain numpy data: {model: "GBR", mean, s
 max_depth, feature, threshold, value, q}, which GBRModel predicts from (edgedet_gbr_model_predict) and the
 offloading cascade loads as kind "gbr".
 """
-import argparse
 import ctypes
 import math
-import os
-import pickle
 import time
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import ops
+from . import estimator, ops
+from ._saved import DeviceModel, open_model, scaler
 from .regress import _Folds
 
 NAMES = {"GBR": "Gradient Boosting Regressor"}
@@ -56,11 +53,6 @@ class GBROpt:
 
 
 _GBROPT = GBROpt()
-
-
-def _need_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("edgeml_amd.gbr needs an MI355X (HIP) device; there is no CPU path")
 
 
 def check_opts(opts):
@@ -90,7 +82,7 @@ def fit_gbr(features, rewards, split, opts=None, device="cuda"):
     at the end."""
     opts = opts or _GBROPT
     check_opts(opts)
-    _need_device()
+    ops.need_device("edgeml_amd.gbr")
     fo = _Folds(features, rewards, split, device)
     k, N, D, T, depth = fo.k, fo.N, fo.D, int(opts.n_estimators), int(opts.max_depth)
     if not np.all(np.isfinite(fo.x)) or not np.all(np.isfinite(fo.y)):
@@ -154,39 +146,29 @@ FITS = {"GBR": fit_gbr}
 
 
 # ------------------------------------------------------------------------------------------- saved model
-class GBRModel:
+class GBRModel(DeviceModel):
     """One fold's trees with its StandardScaler: mean, scale [width], feature int16 [T, 2^depth - 1], threshold
     [T, 2^depth - 1], value [T, 2^(depth+1) - 1], init, learning_rate, max_depth."""
-    kind = "gbr"
+    kind, module = "gbr", "edgeml_amd.gbr"
 
     def __init__(self, mean, scale, feature, threshold, value, init, learning_rate, max_depth):
         self.width, self.T, self.depth = len(mean), len(feature), int(max_depth)
         self.mean, self.scale, self.feature, self.threshold, self.value = mean, scale, feature, threshold, value
         self.init, self.learning_rate = float(init), float(learning_rate)
-        self._dev = None
 
-    def to(self, device):
-        """Upload once per device; returns self."""
-        _need_device()
-        device = torch.device(device)
-        if device.index is None:
-            device = torch.device(device.type, torch.cuda.current_device())
-        if self._dev is None or self._dev["device"] != device:
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-            self._dev = {"device": device, "mean": t(self.mean), "scale": t(self.scale), "feature": t(self.feature),
-                         "threshold": t(self.threshold), "value": t(self.value)}
-        return self
+    def _upload(self, device):
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        return {"mean": t(self.mean), "scale": t(self.scale), "feature": t(self.feature),
+                "threshold": t(self.threshold), "value": t(self.value)}
 
-    def predict_into(self, feat, est, stream=None):
-        """One library call: feat [B, width] float64 and est [B] float64 on the model's device."""
-        d = self._dev
-        if d is None or d["device"] != feat.device:
-            raise ValueError("edgeml_amd.gbr: call to(device) with the features' device first")
-        ops._need_cuda(feat, est)
+    def workspace_bytes(self, B):
+        return 0  # edgedet_gbr_model_predict needs none
+
+    def predict_into(self, feat, est, ws=None, nbr=None, stream=None):
+        """One library call: feat [B, width] float64 and est [B] float64 on the model's device.  ws and nbr are
+        KernelModel.predict_into's, unused here: the cascade calls the three model-backed kinds alike."""
+        d = self._device_rows(feat, est)
         B, p = int(feat.shape[0]), ops._ptr
-        if feat.dtype != torch.float64 or feat.dim() != 2 or feat.shape[1] != self.width or est.dtype != torch.float64 \
-                or est.numel() < B:
-            raise ValueError(f"edgeml_amd.gbr: features [B][{self.width}] and estimates [B] in float64")
         ops.check(ops.lib().edgedet_gbr_model_predict(p(feat), B, self.width, p(d["mean"]), p(d["scale"]),
                                                       p(d["feature"]), p(d["threshold"]), p(d["value"]), self.init,
                                                       self.learning_rate, self.T, self.depth, p(est),
@@ -194,14 +176,7 @@ class GBRModel:
 
     def predict(self, features):
         """Estimates float64 [N] of features [N, ...] (flattened to [N, width])."""
-        _need_device()
-        if self._dev is None:
-            self.to("cuda")
-        dev = self._dev["device"]
-        x = np.asarray(features, dtype=np.float64)
-        x = np.ascontiguousarray(x.reshape(len(x), -1))
-        if x.shape[1] != self.width:
-            raise ValueError(f"edgeml_amd.gbr: the model takes {self.width} features, the rows have {x.shape[1]}")
+        dev, x = self._host_rows(features)
         if len(x) == 0:
             return np.empty(0, np.float64)
         with torch.cuda.device(dev):
@@ -213,24 +188,14 @@ class GBRModel:
 def load(path_or_dict):
     """The GBRModel of a GBR wts<fold>.pickle (a path, or the dict itself); ValueError on anything else, on
     missing keys, on tree arrays of inconsistent shape and on values that are not finite."""
-    if isinstance(path_or_dict, dict):
-        m, what = path_or_dict, "model"
-    else:
-        what = str(path_or_dict)
-        with open(path_or_dict, "rb") as f:
-            m = pickle.load(f)
+    m, what = open_model(path_or_dict)
     if not isinstance(m, dict) or m.get("model") != "GBR":
         raise ValueError(f"{what}: not a wts<fold>.pickle of edgeml_amd.gbr --model-dir")
     missing = [key for key in KEYS if key not in m]
     if missing:
         raise ValueError(f"{what}: a GBR file without {', '.join(repr(key) for key in missing)}")
-    mean = np.ascontiguousarray(np.asarray(m["mean"], np.float64).reshape(-1))
-    scale = np.ascontiguousarray(np.asarray(m["scale"], np.float64).reshape(-1))
+    mean, scale = scaler(what, m)
     D = len(mean)
-    if len(scale) != D or not 1 <= D <= 255:
-        raise ValueError(f"{what}: 'mean' has {D} entries and 'scale' {len(scale)}; the kernels take 1 to 255 features")
-    if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(scale))) or np.any(scale == 0.0):
-        raise ValueError(f"{what}: 'mean' and 'scale' must be finite, and 'scale' without a zero")
     depth, lr, init = int(m["max_depth"]), float(m["learning_rate"]), float(m["init"])
     if not 1 <= depth <= MAX_DEPTH:
         raise ValueError(f"{what}: max_depth = {depth}; 1 to {MAX_DEPTH}")
@@ -260,7 +225,6 @@ def model_data(info, fold):
 
 # --------------------------------------------------------------------------------------------------- CLI
 def main(opts):
-    from . import estimator
     if opts.model not in FITS:
         raise SystemExit(f"edgeml_amd.gbr builds --model GBR (Gradient Boosting Regressor); --model {opts.model} "
                          f"belongs to edgeml_amd.estimator or edgeml_amd.svr, and RFR and SGD are not built (DESIGN.md §7)")
@@ -271,40 +235,15 @@ def main(opts):
         check_opts(fit_opts)
     except ValueError as e:
         raise SystemExit(str(e)) from None
-    features = estimator.load_stage24(opts.data_dir)
-    with np.load(opts.reward_path, allow_pickle=False) as z:
-        reward = z["reward"]
-    assert len(features) == len(reward), "Inconsistent number of feature maps and offloading rewards."
-    split = np.load(opts.split_path, allow_pickle=False)
-    assert len(reward) == split.shape[1], "Inconsistent number of data points from the dataset and the split."
+    features, reward, split = estimator.load_inputs(opts)
     y = estimator.fold_targets(reward, split, opts.normalize, np.float64)
     results, info = fit_gbr(features, y, split, fit_opts)
-    for cv_idx, val_mask in enumerate(split):
-        r = results[cv_idx]
-        tr_mse = float(np.mean((y[cv_idx, ~val_mask] - r["train_est"]) ** 2))
-        va_mse = float(np.mean((y[cv_idx, val_mask] - r["val_est"]) ** 2)) if val_mask.any() else float("nan")
-        print(f"fold {cv_idx + 1}: Trained {NAMES[opts.model]} model with training MSE: {tr_mse:.3f}, "
-              f"validation MSE: {va_mse:.3f}")
-        estimator.save_result(opts.save_dir, r, cv_idx)
-        if opts.model_dir != "":
-            Path(opts.model_dir).mkdir(parents=True, exist_ok=True)
-            with open(os.path.join(opts.model_dir, f"wts{cv_idx + 1}.pickle"), "wb") as f:
-                pickle.dump(model_data(info, cv_idx), f)
+    estimator.report_folds(opts, NAMES[opts.model], y, split, results, lambda fold: model_data(info, fold))
     return results, info
 
 
 def getargs(argv=None):
-    a = argparse.ArgumentParser(prog="python -m edgeml_amd.gbr")
-    a.add_argument("data_dir")
-    a.add_argument("reward_path")
-    a.add_argument("split_path")
-    a.add_argument("save_dir")
-    a.add_argument("--normalize", action="store_true")
-    a.add_argument("--weight", action="store_true")
-    a.add_argument("--stage", type=int, default=24)
-    a.add_argument("--resize", type=int, default=0)
-    a.add_argument("--model", type=str, default="GBR")
-    a.add_argument("--model-dir", type=str, default="")
+    a = estimator.base_parser("GBR", prog="python -m edgeml_amd.gbr")
     a.add_argument("--n-estimators", type=int, default=_GBROPT.n_estimators)
     a.add_argument("--learning-rate", type=float, default=_GBROPT.learning_rate)
     a.add_argument("--max-depth", type=int, default=_GBROPT.max_depth)

@@ -47,6 +47,9 @@ from . import fmt, ops
 
 
 # ---------------------------------------------------------------------------------------- estimator file
+MODEL_KINDS = ("svr", "knr", "gbr")  # an Estimator.model (kpredict.KernelModel, gbr.GBRModel) predicts these
+
+
 class Estimator:
     """A trained reward estimator on `width` stage-24 features: kind "linear" (mean, scale, coef
     float64 [width], intercept), "mlp" (dims, state float32 in estimator.MlpSpec's layout), or "svr" /
@@ -62,7 +65,7 @@ class Estimator:
         """The model's arrays on the device (uploaded once)."""
         if self._dev is None or self._dev[0] != torch.device(device):
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-            if self.kind in ("svr", "knr", "gbr"):
+            if self.kind in MODEL_KINDS:
                 d = {"model": self.model.to(device)}  # uploads (and standardises the stored rows) once
             elif self.kind == "linear":
                 d = {"mean": t(self.mean), "scale": t(self.scale), "coef": t(self.coef),
@@ -75,7 +78,7 @@ class Estimator:
     def workspace_bytes(self, B):
         """Bytes of the per-batch workspace an SVR or KNR model needs (edgedet_kmodel_workspace_size); 0 for
         the other kinds."""
-        return self.model.workspace_bytes(B) if self.kind in ("svr", "knr") else 0
+        return self.model.workspace_bytes(B) if self.kind in MODEL_KINDS else 0
 
     def decide(self, feat, threshold, est, flag, scratch, stream=None):
         """edgedet_offload_decide on feat [B, width] float64 (device): est [B] float64 and flag [B] uint8
@@ -84,15 +87,11 @@ class Estimator:
         kpredict.KernelModel's, then edgedet_offload_flag."""
         B = int(feat.shape[0])
         d = self.device_data(feat.device)
-        if self.kind == "gbr":  # edgedet_gbr_model_predict needs no workspace
-            d["model"].predict_into(feat, est, stream=stream)
-            ops.check(ops.lib().edgedet_offload_flag(ops._ptr(est), B, float(threshold), ops._ptr(flag),
-                                                     ops.stream_handle(stream)))
-            return
-        if self.kind in ("svr", "knr"):
-            if len(scratch) < 3 or scratch[2] is None:
+        if self.kind in MODEL_KINDS:
+            ws = scratch[2] if len(scratch) > 2 else None
+            if ws is None and self.kind != "gbr":  # edgedet_gbr_model_predict needs no workspace
                 raise ValueError(f"the {self.kind} estimator needs its workspace as scratch[2]")
-            d["model"].predict_into(feat, est, scratch[2], stream=stream)
+            d["model"].predict_into(feat, est, ws, stream=stream)
             ops.check(ops.lib().edgedet_offload_flag(ops._ptr(est), B, float(threshold), ops._ptr(flag),
                                                      ops.stream_handle(stream)))
             return
@@ -105,6 +104,12 @@ class Estimator:
                     ops._ptr(scratch[1]))
         ops.check(ops.lib().edgedet_offload_decide(ops._ptr(feat), B, self.width, *args, float(threshold),
                                                    ops._ptr(est), ops._ptr(flag), ops.stream_handle(stream)))
+
+
+def _check_width(path, what, have, width, consistent=True):
+    if have != width or not consistent:
+        raise ValueError(f"{path}: the {what} takes {have} features, the cascade makes {width} "
+                         f"(num_class + 5 k: check --k and --dataset)")
 
 
 def load_estimator(path, width, support=False):
@@ -128,9 +133,7 @@ def load_estimator(path, width, support=False):
         dims = [int(shapes[0][1])] + [int(s[0]) for s in shapes]
         if any(len(s) != 2 for s in shapes) or any(shapes[l][1] != dims[l] for l in range(L)) or dims[-1] != 1:
             raise ValueError(f"{path}: the linear layers {shapes} do not chain to one output")
-        if dims[0] != width:
-            raise ValueError(f"{path}: the MLP takes {dims[0]} features, the cascade makes {width} "
-                             f"(num_class + 5 k: check --k and --dataset)")
+        _check_width(path, "MLP", dims[0], width)
         spec = MlpSpec(dims)
         missing = [k for k in spec.unpack(np.zeros(spec.ns, np.float32)) if k not in named]
         if missing:
@@ -140,28 +143,18 @@ def load_estimator(path, width, support=False):
         m = pickle.load(f)
     if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
         raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
-    if m.get("model") == "GBR":
-        model = gbr.load(m)
-        if model.width != width:
-            raise ValueError(f"{path}: the model takes {model.width} features, the cascade makes {width} "
-                             f"(num_class + 5 k: check --k and --dataset)")
-        return Estimator("gbr", width, model=model)
     if m.get("model") == "SVR" and not support:
         raise ValueError(f"{path}: an SVR file holds support vectors, and the cascade does not predict from them "
                          f"yet; train --model LSVR, LR, EN, BR or CNN")
-    if m.get("model") == "SVR" or (m.get("model") == "KNR" and "train" in m and "target" in m):
-        model = kpredict.load(m)
-        if model.width != width:
-            raise ValueError(f"{path}: the model takes {model.width} features, the cascade makes {width} "
-                             f"(num_class + 5 k: check --k and --dataset)")
+    if m.get("model") in ("GBR", "SVR") or (m.get("model") == "KNR" and "train" in m and "target" in m):
+        model = (gbr if m["model"] == "GBR" else kpredict).load(m)
+        _check_width(path, "model", model.width, width)
         return Estimator(model.kind, width, model=model)
     if m.get("model") == "KNR" or "coef" not in m:
         raise ValueError(f"{path}: a KNR file holds no training rows, so the cascade cannot predict from it; "
                          f"train --model LR, EN, BR or CNN")
     mean, scale, coef = (np.ascontiguousarray(np.asarray(m[k], np.float64).reshape(-1)) for k in ("mean", "scale", "coef"))
-    if not (len(mean) == len(scale) == len(coef) == width):
-        raise ValueError(f"{path}: the model takes {len(coef)} features, the cascade makes {width} "
-                         f"(num_class + 5 k: check --k and --dataset)")
+    _check_width(path, "model", len(coef), width, len(mean) == len(scale) == len(coef))
     return Estimator("linear", width, mean=mean, scale=scale, coef=coef, intercept=float(m["intercept"]))
 
 

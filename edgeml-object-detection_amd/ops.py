@@ -265,6 +265,12 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def need_device(module):
+    """The fits and saved-model predictors run on the device only: refuse, naming the module, where there is none."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{module} needs an MI355X (HIP) device; there is no CPU path")
+
+
 def _need_cuda(*ts):
     for t in ts:
         if t is not None and (not t.is_cuda or not t.is_contiguous()):

@@ -60,11 +60,6 @@ class KNROpt:
 _ENOPT, _BROPT, _KNROPT = ENOpt(), BROpt(), KNROpt()  # the defaults a call without opts uses (regression.py's _*OPT)
 
 
-def _need_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("edgeml_amd.regress needs an MI355X (HIP) device; there is no CPU path")
-
-
 class _Folds:
     """The device arrays every fit shares: features, per-fold targets, training lists, scaler statistics."""
 
@@ -148,7 +143,7 @@ class _Folds:
 
 
 def _start(features, rewards, split, device):
-    _need_device()
+    ops.need_device("edgeml_amd.regress")
     fo = _Folds(features, rewards, split, device)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -232,7 +227,7 @@ def fit_knr(features, rewards, split, opts=None, device="cuda"):
     """KNeighborsRegressor(n_neighbors): exact brute-force neighbours on the standardised rows, ties at the
     k-th distance to the lowest training position, the mean summed in position order."""
     opts = opts or _KNROPT
-    _need_device()
+    ops.need_device("edgeml_amd.regress")
     fo = _Folds(features, rewards, split, device)
     kn = int(opts.n_neighbors)
     for tr in fo.tr:

@@ -24,17 +24,13 @@ which edgeml_amd.offload loads as a linear model; for SVR {model, mean, scale, g
 rows), beta, intercept}, which edgeml_amd.kpredict predicts from (csrc/kpredict.hip) and the cascade loads as
 kind "svr".
 """
-import argparse
-import os
-import pickle
 import time
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import ops
+from . import estimator, ops
 from .regress import _Folds
 
 MAX_SVR_ROWS = 4000  # training rows per fold: the SMO gradient lives in LDS
@@ -64,11 +60,6 @@ class LSVROpt:
 _SVROPT, _LSVROPT = SVROpt(), LSVROpt()  # the defaults a call without opts uses (regression.py's _*OPT)
 
 
-def _need_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("edgeml_amd.svr needs an MI355X (HIP) device; there is no CPU path")
-
-
 def _start(features, rewards, split, device, with_kernel):
     fo = _Folds(features, rewards, split, device)
     torch.cuda.synchronize()
@@ -90,7 +81,7 @@ def fit_svr(features, rewards, split, opts=None, device="cuda"):
     opts = opts or _SVROPT
     if opts.kernel != "rbf":
         raise ValueError(f"edgeml_amd.svr: kernel '{opts.kernel}' is not built; only 'rbf' is")
-    _need_device()
+    ops.need_device("edgeml_amd.svr")
     n_max = int((~np.asarray(split, dtype=bool)).sum(1).max())
     if n_max > MAX_SVR_ROWS:
         raise ValueError(f"edgeml_amd.svr.fit_svr: {n_max} training rows in a fold; the solver takes {MAX_SVR_ROWS}")
@@ -125,7 +116,7 @@ def fit_lsvr(features, rewards, split, opts=None, device="cuda"):
     """LinearSVR(C, epsilon): exact dual coordinate descent in natural order down to a duality gap <= tol, so
     |v - v*| <= sqrt(2 gap) for the unique optimum v* of the primal."""
     opts = opts or _LSVROPT
-    _need_device()
+    ops.need_device("edgeml_amd.svr")
     fo, t0, ws, wb = _start(features, rewards, split, device, False)
     k, N, D, T = fo.k, fo.N, fo.D, int(fo.tr_off[-1])
     beta = torch.zeros(T, dtype=torch.float64, device=device)
@@ -172,49 +163,24 @@ def model_data(name, info, fold, features=None):
 
 
 def main(opts):
-    from . import estimator
     if opts.model not in FITS:
         raise SystemExit(f"edgeml_amd.svr builds --model SVR (Support Vector Regression, rbf) and LSVR (Linear "
                          f"Support Vector Regression); --model {opts.model} belongs to edgeml_amd.estimator")
     if opts.stage != 24:
         raise SystemExit("edgeml_amd.svr runs on the stage-24 output features (--stage 24)")
-    features = estimator.load_stage24(opts.data_dir)
-    with np.load(opts.reward_path, allow_pickle=False) as z:
-        reward = z["reward"]
-    assert len(features) == len(reward), "Inconsistent number of feature maps and offloading rewards."
-    split = np.load(opts.split_path, allow_pickle=False)
-    assert len(reward) == split.shape[1], "Inconsistent number of data points from the dataset and the split."
+    features, reward, split = estimator.load_inputs(opts)
     y = estimator.fold_targets(reward, split, opts.normalize, np.float64)
     fit_opts = None
     if opts.model == "LSVR" and getattr(opts, "tol_rel", None) is not None:
         fit_opts = LSVROpt(tol_rel=opts.tol_rel)
     results, info = FITS[opts.model](features, y, split, fit_opts)
-    for cv_idx, val_mask in enumerate(split):
-        r = results[cv_idx]
-        tr_mse = float(np.mean((y[cv_idx, ~val_mask] - r["train_est"]) ** 2))
-        va_mse = float(np.mean((y[cv_idx, val_mask] - r["val_est"]) ** 2)) if val_mask.any() else float("nan")
-        print(f"fold {cv_idx + 1}: Trained {NAMES[opts.model]} model with training MSE: {tr_mse:.3f}, "
-              f"validation MSE: {va_mse:.3f}")
-        estimator.save_result(opts.save_dir, r, cv_idx)
-        if opts.model_dir != "":
-            Path(opts.model_dir).mkdir(parents=True, exist_ok=True)
-            with open(os.path.join(opts.model_dir, f"wts{cv_idx + 1}.pickle"), "wb") as f:
-                pickle.dump(model_data(opts.model, info, cv_idx, features), f)
+    estimator.report_folds(opts, NAMES[opts.model], y, split, results,
+                           lambda fold: model_data(opts.model, info, fold, features))
     return results, info
 
 
 def getargs(argv=None):
-    a = argparse.ArgumentParser(prog="python -m edgeml_amd.svr")
-    a.add_argument("data_dir")
-    a.add_argument("reward_path")
-    a.add_argument("split_path")
-    a.add_argument("save_dir")
-    a.add_argument("--normalize", action="store_true")
-    a.add_argument("--weight", action="store_true")
-    a.add_argument("--stage", type=int, default=24)
-    a.add_argument("--resize", type=int, default=0)
-    a.add_argument("--model", type=str, default="SVR")
-    a.add_argument("--model-dir", type=str, default="")
+    a = estimator.base_parser("SVR", prog="python -m edgeml_amd.svr")
     a.add_argument("--tol-rel", type=float, default=None,
                    help="LSVR only: stop at a duality gap of this times P(0) (default 1e-10; large datasets want 1e-4)")
     return a.parse_args(argv)

@@ -21,24 +21,24 @@ import build as B  # noqa: E402
 
 
 def assembly(src):
+    """The gfx950 assembly of one csrc file (the tree's or a copy elsewhere) under build.py's flags for its name."""
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
     B.write_tile_table(objdir)
     with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "layers.s")
-        cmd = [B.hipcc(), *B.FLAGS, *B.FILE_FLAGS.get("layers.hip", []), "-I", objdir, "-I", os.path.join(PKG, "csrc"),
-               "--cuda-device-only", "-S", src, "-o", out]
+        out = os.path.join(td, "kernels.s")
+        cmd = [B.hipcc(), *B.FLAGS, *B.FILE_FLAGS.get(os.path.basename(src), []), "-I", objdir, "-I",
+               os.path.join(PKG, "csrc"), "--cuda-device-only", "-S", src, "-o", out]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise SystemExit(r.stderr)
         return open(out).read()
 
 
-def kernels(asm):
-    """name -> (instruction lines, trailing metadata comment lines) of every ssd_stem_kernel function."""
+def kernels(asm, name=r"_ZN7edgedet15ssd_stem_kernel\w+"):
+    """mangled name -> (instruction lines, trailing metadata comment lines) of every function whose name matches."""
     out = {}
-    for m in re.finditer(r"^(_ZN7edgedet15ssd_stem_kernel\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:\n(.*?)^; COMPUTE_PGM_RSRC2", asm,
-                         re.S | re.M):
+    for m in re.finditer(r"^(%s):[^\n]*\n(.*?)^\.Lfunc_end\d+:\n(.*?)^; COMPUTE_PGM_RSRC2" % name, asm, re.S | re.M):
         body = [ln.split(";")[0].strip() for ln in m.group(2).splitlines()]
         out[m.group(1)] = ([ln for ln in body if ln and not ln.endswith(":") and not ln.startswith(".")], m.group(3))
     return out
