@@ -12,10 +12,21 @@
 //           detector plan reads (the CLI's input layout), one thread per output pixel pair.
 // All arithmetic is the reference decoder's integer arithmetic (csrc/jpeg_core.hpp), so the bytes equal
 // the host decoder's (tests/test_jpeg.py on the host checker, tests/test_gpu_jpeg.py on the device).
-// Supported: 8-bit baseline / extended sequential Huffman JPEGs, 1 (gray) or 3 (YCbCr) components,
-// 4:4:4, 4:2:2 (h2v1) and 4:2:0 (h2v2) sampling, restart intervals, one or several scans.  Anything else
+// Supported: 8-bit baseline / extended sequential Huffman JPEGs (SOF0 / SOF1, 8- or 16-bit quantisation
+// tables), 1 (gray) or 3 (YCbCr) components, 4:4:4, 4:2:2 (h2v1) and 4:2:0 (h2v2) sampling, restart
+// intervals, one or several scans (interleaved, per component or mixed; a component no scan names decodes
+// as zero coefficients).  As in libjpeg, a chroma component whose downsampled width is 2 or less is
+// replicated, not filtered (the narrow-image rule, jpeg_core.hpp), and a component's quantisation table is
+// latched when the first scan that names it starts: a DQT that redefines the table id later applies only
+// to components not yet scanned, and a scan whose component has no table yet is an error.  Anything else
 // (progressive, arithmetic coding, 12-bit, CMYK / RGB JPEGs, other samplings) reports "unsupported" and
 // the caller decodes that image on the host.
+// Reject policy: the packet holds only what the file's own bits say.  libjpeg decodes damaged entropy
+// data with a warning (zero bits after a premature marker or end of file, resynchronisation on a missing
+// or out-of-sequence RSTn); this decoder does not emulate that, it rejects such a file (< 0 from
+// Decoder::run) and the batch path hands it to the host decoder: a scan that consumed bits its data did
+// not supply, a restart boundary not followed by the RSTn expected in sequence, an interleaved scan whose
+// components are not in frame order, a bad Huffman code.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -106,6 +117,7 @@ struct BitReader {
     uint64_t acc = 0;
     int bits = 0;
     bool marker = false;  // hit a marker: feed zeros (libjpeg's behaviour at a premature marker)
+    int fed = 0;          // zero bits fed since the last restart, past a marker or the end of the input
     void fill() {
         // fast path: the next 8 bytes hold no 0xFF (no stuffing, no marker): take the whole bytes that fit
         if (!marker && pos + 8 <= n) {
@@ -123,7 +135,8 @@ struct BitReader {
         }
         while (bits <= 56) {
             uint32_t byte = 0;
-            if (!marker && pos < n) {
+            const bool supplied = !marker && pos < n;
+            if (supplied) {
                 byte = d[pos];
                 if (byte == 0xFF) {
                     const uint32_t nx = pos + 1 < n ? d[pos + 1] : 0;
@@ -137,6 +150,7 @@ struct BitReader {
                     ++pos;
                 }
             }
+            if ((!supplied || marker) && fed < 128) fed += 8;  // (saturates: the buffer holds 64 bits)
             acc |= (uint64_t)byte << (56 - bits);
             bits += 8;
         }
@@ -155,15 +169,22 @@ struct BitReader {
         skip(k);
         return v;
     }
-    void reset_at_restart() {  // discard the partial byte, skip to and past the RSTn marker
+    // The fed zeros are the buffer's tail (every byte after the first fed one is fed too), so the
+    // decoder consumed bits the data did not supply exactly when fewer bits are left than were fed.
+    // The reader's look-ahead into a closing marker feeds zeros as well, but leaves them in the buffer.
+    bool overran() const { return bits < fed; }
+    // At a restart boundary: discard the partial byte and step past RST<k>, which must be the next
+    // marker.  Every byte of a well-formed interval holds at least one coded bit, so the reader has
+    // taken them all and stands at the marker (or the fill 0xFF bytes before it).
+    bool restart_marker(int k) {
         acc = 0;
         bits = 0;
+        fed = 0;
         marker = false;
-        while (pos + 1 < n && !(d[pos] == 0xFF && d[pos + 1] >= 0xD0 && d[pos + 1] <= 0xD7)) {
-            if (d[pos] == 0xFF && d[pos + 1] != 0x00 && d[pos + 1] != 0xFF) return;  // another marker: leave it
-            ++pos;
-        }
-        if (pos + 1 < n) pos += 2;
+        while (pos + 1 < n && d[pos] == 0xFF && d[pos + 1] == 0xFF) ++pos;
+        if (pos + 1 >= n || d[pos] != 0xFF || d[pos + 1] != 0xD0 + k) return false;
+        pos += 2;
+        return true;
     }
 };
 
@@ -197,6 +218,10 @@ struct Decoder {
     Comp comp[3];
     int16_t q[4][64];
     bool qset[4] = {false, false, false, false};
+    // each component's table as it stood when the first scan that names the component started
+    // (libjpeg's latch_quant_tables): a later DQT of the same id does not reach it
+    int16_t qcomp[3][64];
+    bool latched[3] = {false, false, false};
     Huff dc[4], ac[4];
     bool adobe = false;
     int adobe_transform = -1;
@@ -344,6 +369,15 @@ struct Decoder {
                     td[i] = s[2 + 2 * i] >> 4;
                     ta[i] = s[2 + 2 * i] & 15;
                     if (td[i] > 3 || ta[i] > 3 || !dc[td[i]].present || !ac[ta[i]].present) return fail("missing Huffman table");
+                    // interleaved components follow the frame's order (T.81 B.2.3); libjpeg refuses others
+                    if (i > 0 && sc[i] <= sc[i - 1]) return fail("SOS components out of frame order");
+                }
+                for (int i = 0; i < ns; ++i) {
+                    const int c = sc[i];
+                    if (latched[c]) continue;
+                    if (!qset[comp[c].tq]) return fail("SOS names a component whose quantisation table is not defined yet");
+                    std::memcpy(qcomp[c], q[comp[c].tq], sizeof(qcomp[c]));
+                    latched[c] = true;
                 }
                 const int Ss = s[1 + 2 * ns], Se = s[2 + 2 * ns], AhAl = s[3 + 2 * ns];
                 if (Ss != 0 || Se != 63 || AhAl != 0) return unsupported("spectral selection");
@@ -356,10 +390,10 @@ struct Decoder {
             pos += len;
         }
         if (!have_frame) return fail("no frame");
-        for (int c = 0; c < ncomp; ++c)
-            if (!qset[comp[c].tq]) return fail("missing quantisation table");
+        if (!latched[0] && !latched[1] && !latched[2]) return fail("no scan");
+        // a component no scan named has no coefficients, and needs no table
         for (int c = 0; c < 3; ++c)
-            for (int k = 0; k < 64; ++k) hd.quant[c][k] = c < ncomp ? q[comp[c].tq][k] : 0;
+            for (int k = 0; k < 64; ++k) hd.quant[c][k] = c < ncomp && latched[c] ? qcomp[c][k] : 0;
         hd.nnz = (int32_t)coef.size();
         hd.off_blocks = (int32_t)((sizeof(Header) + 15) / 16 * 16);
         hd.off_coef = hd.off_blocks + 8 * hd.nblocks;
@@ -391,10 +425,12 @@ struct Decoder {
             mcus_y = hd.mcus_y;
         }
         const int total = mcus_x * mcus_y;
-        int todo = restart;
+        int todo = restart, next_rst = 0;
         for (int mcu = 0; mcu < total; ++mcu) {
             if (restart && todo == 0) {
-                br.reset_at_restart();
+                if (br.overran()) return fail("entropy data ends inside a restart interval");
+                if (!br.restart_marker(next_rst)) return fail("restart marker missing or out of sequence");
+                next_rst = (next_rst + 1) & 7;
                 pred[0] = pred[1] = pred[2] = 0;
                 todo = restart;
             }
@@ -412,6 +448,7 @@ struct Decoder {
             }
             --todo;
         }
+        if (br.overran()) return fail("entropy data ends inside the scan");
         // the scan ends at the next marker that is not a stuffed 0xFF00, a fill 0xFF or an RSTn: the
         // reader may stop short of it (bits already buffered), so search from where it stopped
         size_t p = std::min(br.pos, n);
@@ -539,11 +576,13 @@ EDGEDET_HD int sample(const Planes& P, int c, int y, int x) {
     return P.base[(int64_t)hd.block_base[c] * 64 + (int64_t)y * hd.bw[c] * 8 + x];
 }
 
-// fancy-upsampled chroma sample of component c at output (y, x) (h2v2, h2v1 or none)
+// upsampled chroma sample of component c at output (y, x) (h2v2, h2v1 or none): fancy, except that a
+// component of downsampled width 2 or less is replicated on both axes (jpeg_core.hpp; uniform per image)
 EDGEDET_HD int chroma(const Planes& P, int c, int y, int x) {
     const Header& hd = *P.hd;
     const int cw = hd.cw[c], chh = hd.ch[c];
     if (hd.hmax == 1 && hd.vmax == 1) return sample(P, c, y, x);
+    if (cw <= 2) return sample(P, c, hd.vmax == 1 ? y : y >> 1, x >> 1);
     if (hd.vmax == 1) {  // h2v1
         const int cx = x >> 1;
         const int in = sample(P, c, y, cx);

@@ -9,7 +9,10 @@
 //     PASS1_BITS 2, the twelve FIX_* constants, DESCALE = round-half-up arithmetic shift), output
 //     through the post-IDCT range-limit table (x & 1023 -> clamp(x + 128), wrapping beyond +-512);
 //   * "fancy" (triangular) chroma upsampling (jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample,
-//     with the edge columns and rows replicated and the +8/+7 and +1/+2 rounding biases);
+//     with the edge columns and rows replicated and the +8/+7 and +1/+2 rounding biases), which
+//     jinit_upsampler selects only for a component whose downsampled_width is above 2: at 2 or below it
+//     takes h2v1_upsample / h2v2_upsample, plain replication, and for h2v2 on both axes (no vertical
+//     filter either): a 4:2:2 or 4:2:0 image up to 4 pixels wide has replicated chroma;
 //   * YCbCr -> RGB (jdcolor.c ycc_rgb_convert: SCALEBITS 16 fixed-point tables, clamp to 0..255).
 // Grayscale images become RGB by replication (PIL's convert("RGB") of an "L" image).
 #pragma once
@@ -121,6 +124,7 @@ EDGEDET_HD void ycc_rgb(int32_t y, int32_t cb, int32_t cr, uint8_t& r, uint8_t& 
 //         (4 cs(0) + 8) >> 4; odd x: (3 cs(c) + cs(c+1) + 7) >> 4, last column (4 cs(cw-1) + 7) >> 4.
 //   h2v1: cs(c) = row[c];  even x: (3 cs(c) + cs(c-1) + 1) >> 2, first column cs(0);
 //         odd x: (3 cs(c) + cs(c+1) + 2) >> 2, last column cs(cw-1).
+//   cw <= 2 (either): the sample at (y / vmax, x / 2), no filter on either axis.
 
 }  // namespace jpeg
 }  // namespace edgedet
