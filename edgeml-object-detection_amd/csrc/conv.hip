@@ -15,6 +15,17 @@
 // wave contributes k = 16h + 8q + t (q, t loop indices), so both operands are read from LDS as
 // contiguous f32x4s (ds_read_b128) from K-contiguous rows padded to 36 floats (conflict-free
 // for the b128 lane groups).
+//
+// Map of the file:
+//   shared pieces   conv_row_offset, in_transform, xcd_tile (block order), tap_of (GEMM column ->
+//                   filter tap), conv_epilogue
+//   LDS kernels     conv_mfma_kernel (fp32 MFMA), conv_x6_kernel (bf16x6, 16-deep stages),
+//                   conv_x6b_body (bf16x6, 32-deep swizzled stages; conv_x6b_kernel and the grouped
+//                   conv_x6b_group_kernel wrap it), split_act_kernel (its pre-split input)
+//   pointwise       pw_mfma_kernel, pw_splitk_kernel, pw_stream_kernel: 1x1 operands straight from
+//                   global memory, no LDS staging
+//   launchers       launch_*, choose_tile, conv_prepare, conv_resolve_tile, conv_launch (tile id ->
+//                   kernel; the ids are ConvTile, kernels.hpp), conv_group_launch, the C entry points
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -74,7 +85,29 @@ __device__ __forceinline__ void act_tile(floatx16 (&acc)[TM][TN]) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = apply_act(acc[i][j][r], ACT);
 }
 
-// Epilogue shared by both conv kernels.  Row of (i, r) = row0 + 32i + (r&3) + 8(r>>2) + 4h (the
+// XCD-aware, bijective block remap: blocks that share an XCD (bid % 8) get consecutive tiles,
+// which share their A (activation) panel.
+__device__ __forceinline__ int xcd_tile(int bid, int nwg) {
+    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
+}
+
+// Filter tap and channel of GEMM column k (the weight layout, k = (kh * KW + kw) * Cin + ci); the
+// columns of the zero padding past K are not valid.  khw = KH * KW, which every caller holds from
+// before its K loop (taking the product in here reorders the code of half the kernels).
+struct Tap {
+    int kh, kw, ci;
+    bool valid;
+};
+__device__ __forceinline__ Tap tap_of(const ConvParams& p, int k, int khw) {
+    const int tap = (int)fdiv((uint32_t)k, p.div_cin);
+    const int ci = k - tap * p.Cin;
+    const int kh = (int)fdiv((uint32_t)tap, p.div_kw);
+    const int kw = tap - kh * p.KW;
+    return {kh, kw, ci, tap < khw};
+}
+
+// Epilogue shared by the conv kernels.  Row of (i, r) = row0 + 32i + (r&3) + 8(r>>2) + 4h (the
 // 32x32 MFMA C layout), column of j = col0 + 32j + (lane & 31).  L16: the 32 x 32 block (i, j) holds
 // four 16x16 MFMA C tiles, register r in tile q = r >> 2 (row half q >> 1, column half q & 1): row
 // row0 + 32i + 16((r>>3)&1) + 4(lane>>4) + (r&3), column col0 + 32j + 16((r>>2)&1) + (lane&15).
@@ -177,16 +210,10 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_mfma_kernel(ConvParams p) {
     const int wave_m = wid / WN;
     const int wave_n = wid % WN;
 
-    // XCD-aware, bijective block remap: blocks that share an XCD (bid % 8) get consecutive tiles,
-    // which share their A (activation) panel.
     const int nmt = (p.M + BM - 1) / BM;
     const int nnt = (p.Cout + BN - 1) / BN;
     const int nwg = nmt * nnt;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    const int bid = xcd_tile(blockIdx.x, nwg);
     const int mt = bid / nnt;
     const int nt = bid % nnt;
     const int m0 = mt * BM;
@@ -227,19 +254,14 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_mfma_kernel(ConvParams p) {
     f32x4 ra[AJ], rb[BJ];
 
     auto load_stage = [&](int k0) {
-        const int k = k0 + c4 * 4;
-        const int tap = (int)fdiv((uint32_t)k, p.div_cin);
-        const int ci = k - tap * p.Cin;
-        const int kh = (int)fdiv((uint32_t)tap, p.div_kw);
-        const int kw = tap - kh * p.KW;
-        const bool kval = tap < KHW;
+        const Tap t = tap_of(p, k0 + c4 * 4, KHW);
 #pragma unroll
         for (int j = 0; j < AJ; ++j) {
-            const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
+            const int ih = a_ih0[j] + t.kh, iw = a_iw0[j] + t.kw;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (kval && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
-                v = *reinterpret_cast<const f32x4*>(p.x + a_base[j] + (int64_t)(ih * p.W + iw) * p.x_pstride + ci);
-                v = in_transform(p, v, a_b[j], ci);
+            if (t.valid && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
+                v = *reinterpret_cast<const f32x4*>(p.x + a_base[j] + (int64_t)(ih * p.W + iw) * p.x_pstride + t.ci);
+                v = in_transform(p, v, a_b[j], t.ci);
             }
             ra[j] = v;
         }
@@ -669,11 +691,7 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_x6_kernel(ConvParams p) {
     const int nmt = (p.M + BM - 1) / BM;
     const int nnt = (p.Cout + BN - 1) / BN;
     const int nwg = nmt * nnt;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    const int bid = xcd_tile(blockIdx.x, nwg);
     const int mt = bid / nnt;
     const int nt = bid % nnt;
     const int m0 = mt * BM;
@@ -738,6 +756,7 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_x6_kernel(ConvParams p) {
     auto load_stage = [&](Regs& R, int k0) {
         R.sg = ((k0 >> 5) & 1) ? -1.f : 1.f;
         if constexpr (UT) {
+            // (the stage's uniform tap, not through tap_of: that reorders these kernels' code)
             const int tap = (int)fdiv((uint32_t)k0, p.div_cin);
             const int ci = k0 - tap * p.Cin + c4 * 4;
             const int kh = (int)fdiv((uint32_t)tap, p.div_kw);
@@ -754,19 +773,14 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_x6_kernel(ConvParams p) {
                 R.a[j] = v;
             }
         } else {
-            const int k = k0 + c4 * 4;
-            const int tap = (int)fdiv((uint32_t)k, p.div_cin);
-            const int ci = k - tap * p.Cin;
-            const int kh = (int)fdiv((uint32_t)tap, p.div_kw);
-            const int kw = tap - kh * p.KW;
-            const bool kval = tap < KHW;
+            const Tap t = tap_of(p, k0 + c4 * 4, KHW);
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
-                const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
+                const int ih = a_ih0[j] + t.kh, iw = a_iw0[j] + t.kw;
                 f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (kval && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
-                    v = *reinterpret_cast<const f32x4*>(p.x + a_base[j] + (int64_t)(ih * p.W + iw) * p.x_pstride + ci);
-                    if constexpr (XF) v = in_transform(p, v, a_b[j], ci);
+                if (t.valid && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
+                    v = *reinterpret_cast<const f32x4*>(p.x + a_base[j] + (int64_t)(ih * p.W + iw) * p.x_pstride + t.ci);
+                    if constexpr (XF) v = in_transform(p, v, a_b[j], t.ci);
                 }
                 R.a[j] = v;
             }
@@ -914,11 +928,7 @@ __device__ __forceinline__ void conv_x6b_body(const ConvParams& p, const int blk
     const int nnt = (p.Cout + BN - 1) / BN;
     const int nwg = nmt * nnt;
     const int ksp = p.ksplit > 1 ? 2 : 1;  // split-K: block 2t + s takes K half s of tile t
-    int bid = blk / ksp;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    const int bid = xcd_tile(blk / ksp, nwg);
     const int m0 = (bid / nnt) * BM;
     const int n0 = (bid % nnt) * BN;
 
@@ -979,11 +989,6 @@ __device__ __forceinline__ void conv_x6b_body(const ConvParams& p, const int blk
     struct StageK {
         int k0, kh, kw, ci;
     };
-    auto stage_tap = [&](const StageK& sk, int& kh, int& kw, int& ci0) {
-        kh = sk.kh;
-        kw = sk.kw;
-        ci0 = sk.ci;
-    };
     auto load_stage = [&](Regs& R, const StageK& sk, int bbuf) {
         const int k0 = sk.k0;
         R.sg = ((k0 >> 5) & 1) ? -1.f : 1.f;  // the sign the split weights carry for this K block
@@ -1006,15 +1011,13 @@ __device__ __forceinline__ void conv_x6b_body(const ConvParams& p, const int blk
             }
         }
         if constexpr (PS) {
-            int kh, kw, ci0;
-            stage_tap(sk, kh, kw, ci0);
             if constexpr (GL) {
-                const unsigned short* xt = x3 + X3Z + (int64_t)(kh * p.W + kw) * p.Cin + ci0;
+                const unsigned short* xt = x3 + X3Z + (int64_t)(sk.kh * p.W + sk.kw) * p.Cin + sk.ci;
 #pragma unroll
                 for (int j = 0; j < AJ; ++j) {
                     const int row = a_row0 + AST * j;
                     const int lc = (lane & 3) ^ swz_key(row);  // swizzle on the source address
-                    const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
+                    const int ih = a_ih0[j] + sk.kh, iw = a_iw0[j] + sk.kw;
                     const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
@@ -1026,10 +1029,10 @@ __device__ __forceinline__ void conv_x6b_body(const ConvParams& p, const int blk
                             16, 0, 0);
                 }
             } else {
-                const unsigned short* xt = x3 + X3Z + (int64_t)(kh * p.W + kw) * p.Cin + ci0 + 8 * (tid & 3);
+                const unsigned short* xt = x3 + X3Z + (int64_t)(sk.kh * p.W + sk.kw) * p.Cin + sk.ci + 8 * (tid & 3);
 #pragma unroll
                 for (int j = 0; j < AJ; ++j) {
-                    const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
+                    const int ih = a_ih0[j] + sk.kh, iw = a_iw0[j] + sk.kw;
                     const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
@@ -1050,14 +1053,12 @@ __device__ __forceinline__ void conv_x6b_body(const ConvParams& p, const int blk
                 R.a[j] = v;
             }
         } else if constexpr (UT) {
-            int kh, kw, ci0;
-            stage_tap(sk, kh, kw, ci0);
-            const int ci = ci0 + c8 * 4;
-            const float* xt = p.x + (int64_t)(kh * p.W + kw) * p.x_pstride + ci;
+            const int ci = sk.ci + c8 * 4;
+            const float* xt = p.x + (int64_t)(sk.kh * p.W + sk.kw) * p.x_pstride + ci;
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
                 // (a branch-free form, padding taps loading from p.x and zeroed, measured 3-5% slower)
-                const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
+                const int ih = a_ih0[j] + sk.kh, iw = a_iw0[j] + sk.kw;
                 const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
                 f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (ok) {
@@ -1067,19 +1068,14 @@ __device__ __forceinline__ void conv_x6b_body(const ConvParams& p, const int blk
                 R.a[j] = v;
             }
         } else {
-            const int k = k0 + c8 * 4;
-            const int tap = (int)fdiv((uint32_t)k, p.div_cin);
-            const int ci = k - tap * p.Cin;
-            const int kh = (int)fdiv((uint32_t)tap, p.div_kw);
-            const int kw = tap - kh * p.KW;
-            const bool kval = tap < KHW;
+            const Tap t = tap_of(p, k0 + c8 * 4, KHW);
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
-                const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
+                const int ih = a_ih0[j] + t.kh, iw = a_iw0[j] + t.kw;
                 f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (kval && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
-                    v = *reinterpret_cast<const f32x4*>(p.x + a_base[j] + (int64_t)(ih * p.W + iw) * p.x_pstride + ci);
-                    if constexpr (XF) v = in_transform(p, v, a_b[j], ci);
+                if (t.valid && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
+                    v = *reinterpret_cast<const f32x4*>(p.x + a_base[j] + (int64_t)(ih * p.W + iw) * p.x_pstride + t.ci);
+                    if constexpr (XF) v = in_transform(p, v, a_b[j], t.ci);
                 }
                 R.a[j] = v;
             }
@@ -1416,8 +1412,7 @@ struct X6bVariant {
     bool operator==(const X6bVariant& o) const { return xf == o.xf && ut == o.ut && p1 == o.p1; }
 };
 static X6bVariant x6b_variant(const ConvParams& p) {
-    return {p.in_scale || p.in_shift || p.in_relu, p.Cin % BK6B == 0,
-            p.lin_x && p.KH == 1 && p.KW == 1 && p.Cin % 4 == 0};
+    return {has_in_transform(p), p.Cin % BK6B == 0, p.lin_x && p.KH == 1 && p.KW == 1 && p.Cin % 4 == 0};
 }
 // kernel(XF, UT, P1) for the variant's flags as compile-time constants (std::bool_constant): all eight
 // kernels are instantiated, the variant's is returned.
@@ -1430,11 +1425,16 @@ static auto x6b_select(X6bVariant v, F kernel) {
     return v.xf ? ut(T{}) : ut(N{});
 }
 
-template <int BM = 256, int PF = 1, int BN = 128>
-static int launch_x6b(const ConvParams& p0, hipStream_t s) {
-    ConvParams p = p0;
+// The weight operand of a bf16x6 kernel with kdepth-deep K stages.
+static int require_w3(const ConvParams& p, int kdepth) {
     EDGEDET_REQUIRE(p.w3 && ((uintptr_t)p.w3 & 15) == 0, "conv bf16x6: needs 16-byte aligned split weight planes");
-    EDGEDET_REQUIRE(p.Kpad % BK6B == 0, "conv bf16x6: Kpad must be a multiple of 32");
+    EDGEDET_REQUIRE(p.Kpad % kdepth == 0, "conv bf16x6: Kpad must be a multiple of " + std::to_string(kdepth));
+    return 0;
+}
+
+template <int BM = 256, int PF = 1, int BN = 128>
+static int launch_x6b(const ConvParams& p, hipStream_t s) {
+    if (require_w3(p, BK6B)) return -1;
     if (p.ksplit > 1)
         EDGEDET_REQUIRE(p.ksplit == 2 && !p.res && p.act == 0 && p.Kpad >= 2 * BK6B,
                         "conv split-K: 2 halves, no residual, no activation (y must be zeroed)");
@@ -1464,7 +1464,7 @@ static int launch_x6b_group(ConvGroup& g, hipStream_t s) {
     int64_t total = 0;
     for (int k = 0; k < g.n; ++k) {
         const ConvParams& q = g.p[k];
-        EDGEDET_REQUIRE(q.w3 && ((uintptr_t)q.w3 & 15) == 0 && q.Kpad % BK6B == 0 && q.ksplit <= 1,
+        EDGEDET_REQUIRE(require_w3(q, BK6B) == 0 && q.ksplit <= 1,
                         "conv group: bf16x6 members with 16-byte aligned split planes, Kpad % 32 == 0, no split-K");
         EDGEDET_REQUIRE(x6b_variant(q) == v, "conv group: members of one kernel variant");
         g.start[k] = (int)total;
@@ -1499,11 +1499,10 @@ __global__ void split_bf16x3_kernel(const float* __restrict__ w, int64_t n, int6
 template <int WM, int WN, int TM, int TN>
 static int launch_x6(const ConvParams& p, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    EDGEDET_REQUIRE(p.w3 && ((uintptr_t)p.w3 & 15) == 0, "conv bf16x6: needs 16-byte aligned split weight planes");
-    EDGEDET_REQUIRE(p.Kpad % BK6 == 0, "conv bf16x6: Kpad must be a multiple of 16");
+    if (require_w3(p, BK6)) return -1;
     const int64_t nwg = cdiv(p.M, BM) * cdiv(p.Cout, BN);
     EDGEDET_REQUIRE(nwg < (1ll << 31), "conv grid too large");
-    const bool xf = p.in_scale || p.in_shift || p.in_relu, ut = (p.Cin & 15) == 0;
+    const bool xf = has_in_transform(p), ut = (p.Cin & 15) == 0;
     auto k = xf ? (ut ? conv_x6_kernel<WM, WN, TM, TN, true, true> : conv_x6_kernel<WM, WN, TM, TN, true, false>)
                 : (ut ? conv_x6_kernel<WM, WN, TM, TN, false, true> : conv_x6_kernel<WM, WN, TM, TN, false, false>);
     hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WM * WN * 64), 0, s, p);
@@ -1542,8 +1541,7 @@ static int launch_pw_stream_nk(const ConvParams& p, hipStream_t s) {
     const int ncg = (p.Cout + 32 * NB - 1) / (32 * NB);
     const int64_t waves = cdiv(p.M, 32) * ncg;
     const unsigned g = (unsigned)std::min<int64_t>(cdiv(waves, 4), pw_stream_max_wg());
-    const bool xf = p.in_scale || p.in_shift || p.in_relu;
-    auto k = xf ? pw_stream_kernel<NB, KJ, true, PF> : pw_stream_kernel<NB, KJ, false, PF>;
+    auto k = has_in_transform(p) ? pw_stream_kernel<NB, KJ, true, PF> : pw_stream_kernel<NB, KJ, false, PF>;
     hipLaunchKernelGGL(k, dim3(g), dim3(256), 0, s, p, ncg);
     EDGEDET_LAUNCH_CHECK();
     return 0;
@@ -1592,16 +1590,18 @@ static int launch_cfg(const ConvParams& p, hipStream_t s) {
 // Tile choice: the direct pointwise kernel for narrow-K 1x1 layers (HBM-bound, no reuse to stage);
 // otherwise the largest LDS-staged tile that still gives about one workgroup per CU.
 static int choose_tile(const ConvParams& p) {
-    if (p.lin_x && p.Kpad >= 256 && p.Cout <= 96) return p.Cout <= 32 ? 13 : (p.Cout <= 64 ? 14 : 13);
+    if (p.lin_x && p.Kpad >= 256 && p.Cout <= 96)
+        return p.Cout > 32 && p.Cout <= 64 ? TILE_PW_SPLITK4_32x64 : TILE_PW_SPLITK4_32x32;
     if (p.lin_x && (p.Kpad <= 128 || p.Cout <= 32)) {
-        if (p.Cout <= 32) return 15;
+        if (p.Cout <= 32) return TILE_PW_64x32;
         const int64_t w22 = cdiv(p.M, 64) * cdiv(p.Cout, 64);
-        return w22 >= 4 * 256 ? 10 : 12;
+        return w22 >= 4 * 256 ? TILE_PW_64x64 : TILE_PW_32x64;
     }
     struct C { int tile, bm, bn; };
-    const C cands_wide[] = {{3, 128, 128}, {2, 128, 64}, {5, 64, 64}, {6, 32, 32}};
-    const C cands_mid[] = {{2, 128, 64}, {5, 64, 64}, {6, 32, 32}};
-    const C cands_narrow[] = {{1, 128, 32}, {6, 32, 32}};
+    const C cands_wide[] = {{TILE_F32_128x128, 128, 128}, {TILE_F32_128x64, 128, 64}, {TILE_F32_64x64, 64, 64},
+                            {TILE_F32_32x32, 32, 32}};
+    const C cands_mid[] = {{TILE_F32_128x64, 128, 64}, {TILE_F32_64x64, 64, 64}, {TILE_F32_32x32, 32, 32}};
+    const C cands_narrow[] = {{TILE_F32_128x32, 128, 32}, {TILE_F32_32x32, 32, 32}};
     const C* c = p.Cout > 64 ? cands_wide : (p.Cout > 32 ? cands_mid : cands_narrow);
     const int nc = p.Cout > 64 ? 4 : (p.Cout > 32 ? 3 : 2);
     for (int i = 0; i < nc; ++i)
@@ -1638,11 +1638,10 @@ int conv_prepare(ConvParams& p) {
 int conv_resolve_tile(const ConvParams& p, int tile) {
     if (tile <= TILE_AUTO) {
         tile = choose_tile(p);
-        if (p.w3 && tile >= 2 && tile <= 4) {
-            tile += 20;
-            // large problems: the 32-deep-stage 256 x 128 tile (>= 2 workgroups per CU)
-            if (tile >= 23 && cdiv(p.M, 256) * cdiv(p.Cout, 128) >= 512) tile = TILE_X6B_256x128;
-        }
+        if (p.w3) tile = tile_x6_form(tile);
+        // large problems: the 32-deep-stage 256 x 128 tile (>= 2 workgroups per CU)
+        if ((tile == TILE_X6_128x128 || tile == TILE_X6_256x128) && cdiv(p.M, 256) * cdiv(p.Cout, 128) >= 512)
+            tile = TILE_X6B_256x128;
     }
     return tile;
 }
@@ -1652,46 +1651,39 @@ int conv_launch(ConvParams p, int tile, hipStream_t s) {
     const int rc = conv_prepare(p);
     if (rc) return rc;
     tile = conv_resolve_tile(p, tile);
-    if (tile >= 10 && tile <= 17)  // the direct and split-K pointwise tiles
-        EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
-    switch (tile) {
-        case 21: return launch_x6<2, 2, 1, 1>(p, s);  // 64 x 64, bf16x6
-        case 22: return launch_x6<2, 2, 2, 1>(p, s);  // 128 x 64, bf16x6
-        case 23: return launch_x6<2, 2, 2, 2>(p, s);  // 128 x 128, bf16x6
-        case 24: return launch_x6<4, 2, 2, 2>(p, s);  // 256 x 128, bf16x6
-        case 27: return launch_x6<4, 2, 1, 1>(p, s);  // 128 x 64, bf16x6, 8 waves (32 x 32 each)
-        case 28: return launch_x6<4, 2, 1, 2>(p, s);  // 128 x 128, bf16x6, 8 waves (32 x 64 each)
-        // bf16x6 with 32-deep swizzled stages (the named ids: ConvTile, kernels.hpp)
-        case TILE_X6B_256x128: return launch_x6b(p, s);  // 25: 256 x 128
-        case TILE_X6B_256x128_SPLITK: {                  // 26: the same, K split in two halves (atomics into zeroed y)
-            ConvParams q = p;
-            q.ksplit = 2;
-            return launch_x6b(q, s);
-        }
-        case TILE_X6B_128x128: return launch_x6b<128, 1>(p, s);       // 29: 128 x 128, skewed pipeline
-        case 30: return launch_x6b<128, 2>(p, s);                     // the same, two register stages
-        case TILE_X6B_64x128: return launch_x6b<64, 1>(p, s);         // 31: 64 x 128, two workgroups per CU
-        case 32: return launch_x6b<64, 2>(p, s);                      // the same, two register stages
-        case TILE_X6B_128x64: return launch_x6b<128, 1, 64>(p, s);    // 38: 128 x 64 (Cout <= 64 layers)
-        case TILE_X6B_128x256: return launch_x6b<128, 1, 256>(p, s);  // 39: 128 x 256, the A panel read once per Cout = 256 layer
-        case 33:  // streaming 1x1, fp32 MFMA, weights in registers
-        case TILE_PW_STREAM_WAVE:       // 34
-        case TILE_PW_STREAM_WAVE_NOPF:  // 35
-            return launch_pw_stream(p, tile, s);
-        case 1: return launch_cfg<4, 1, 1, 1>(p, s);  // 128 x 32
-        case 2: return launch_cfg<2, 2, 2, 1>(p, s);  // 128 x 64
-        case 3: return launch_cfg<2, 2, 2, 2>(p, s);  // 128 x 128
-        case 4: return launch_cfg<4, 2, 2, 2>(p, s);  // 256 x 128
-        case 5: return launch_cfg<2, 2, 1, 1>(p, s);  // 64 x 64
-        case 6: return launch_cfg<1, 1, 1, 1>(p, s);  // 32 x 32 (one wave)
-        case 10: return launch_pw<2, 2>(p, s);         // direct, 64 x 64 per wave
-        case 11: return launch_pw<4, 1>(p, s);         // direct, 128 x 32 per wave
-        case 12: return launch_pw<1, 2>(p, s);         // direct, 32 x 64 per wave
-        case 15: return launch_pw<2, 1>(p, s);         // direct, 64 x 32 per wave
-        case 13: return launch_pw_splitk<1>(p, s);     // split-K over 4 waves, 32 x 32
-        case 16: return launch_pw_splitk<1, 8>(p, s);  // split-K over 8 waves, 32 x 32
-        case 17: return launch_pw_splitk<2, 8>(p, s);  // split-K over 8 waves, 32 x 64
-        case 14: return launch_pw_splitk<2>(p, s);     // split-K over 4 waves, 32 x 64
+    if (tile_is_pw(tile)) EDGEDET_REQUIRE(p.lin_x, "pw tiles need a 1x1/stride-1 dense input");
+    switch (tile) {  // (the shapes and families of the ids: ConvTile, kernels.hpp)
+        case TILE_X6_64x64: return launch_x6<2, 2, 1, 1>(p, s);
+        case TILE_X6_128x64: return launch_x6<2, 2, 2, 1>(p, s);
+        case TILE_X6_128x128: return launch_x6<2, 2, 2, 2>(p, s);
+        case TILE_X6_256x128: return launch_x6<4, 2, 2, 2>(p, s);
+        case TILE_X6_128x64_W8: return launch_x6<4, 2, 1, 1>(p, s);   // 32 x 32 per wave
+        case TILE_X6_128x128_W8: return launch_x6<4, 2, 1, 2>(p, s);  // 32 x 64 per wave
+        case TILE_X6B_256x128: return launch_x6b(p, s);
+        case TILE_X6B_256x128_SPLITK: p.ksplit = 2; return launch_x6b(p, s);
+        case TILE_X6B_128x128: return launch_x6b<128, 1>(p, s);
+        case TILE_X6B_128x128_PF2: return launch_x6b<128, 2>(p, s);
+        case TILE_X6B_64x128: return launch_x6b<64, 1>(p, s);
+        case TILE_X6B_64x128_PF2: return launch_x6b<64, 2>(p, s);
+        case TILE_X6B_128x64: return launch_x6b<128, 1, 64>(p, s);
+        case TILE_X6B_128x256: return launch_x6b<128, 1, 256>(p, s);
+        case TILE_PW_STREAM:
+        case TILE_PW_STREAM_WAVE:
+        case TILE_PW_STREAM_WAVE_NOPF: return launch_pw_stream(p, tile, s);
+        case TILE_F32_128x32: return launch_cfg<4, 1, 1, 1>(p, s);
+        case TILE_F32_128x64: return launch_cfg<2, 2, 2, 1>(p, s);
+        case TILE_F32_128x128: return launch_cfg<2, 2, 2, 2>(p, s);
+        case TILE_F32_256x128: return launch_cfg<4, 2, 2, 2>(p, s);
+        case TILE_F32_64x64: return launch_cfg<2, 2, 1, 1>(p, s);
+        case TILE_F32_32x32: return launch_cfg<1, 1, 1, 1>(p, s);
+        case TILE_PW_64x64: return launch_pw<2, 2>(p, s);
+        case TILE_PW_128x32: return launch_pw<4, 1>(p, s);
+        case TILE_PW_32x64: return launch_pw<1, 2>(p, s);
+        case TILE_PW_64x32: return launch_pw<2, 1>(p, s);
+        case TILE_PW_SPLITK4_32x32: return launch_pw_splitk<1>(p, s);
+        case TILE_PW_SPLITK8_32x32: return launch_pw_splitk<1, 8>(p, s);
+        case TILE_PW_SPLITK8_32x64: return launch_pw_splitk<2, 8>(p, s);
+        case TILE_PW_SPLITK4_32x64: return launch_pw_splitk<2>(p, s);
         default: EDGEDET_REQUIRE(false, "conv: unknown tile config");
     }
 }

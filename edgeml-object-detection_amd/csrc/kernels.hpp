@@ -212,19 +212,72 @@ struct RetinaNmsParams {
 int gn_stats_launch(const GnParams& p, hipStream_t s);
 int retina_select_launch(const RetinaSelParams& P, SegOut out, hipStream_t s);
 int retina_class_nms_launch(const RetinaNmsParams& P, int B, SegOut out, hipStream_t s);
-// The conv tile ids that code outside conv_launch's switch refers to (conv.hip; that switch is the whole
-// table).  The numbers are frozen: data/conv_tiles_gfx950.json and the Python host use them.
+// The conv tile ids (conv.hip conv_launch's switch gives each its kernel).  The numbers are frozen:
+// data/conv_tiles_gfx950.json and the Python host use them.
 enum ConvTile : int {
     TILE_AUTO = 0,                 // conv_resolve_tile chooses
-    TILE_X6B_256x128 = 25,         // bf16x6, 32-deep swizzled stages; takes the pre-split input (CONV p x3)
+    // fp32 MFMA, LDS-staged (conv_mfma_kernel)
+    TILE_F32_128x32 = 1,
+    TILE_F32_128x64 = 2,
+    TILE_F32_128x128 = 3,
+    TILE_F32_256x128 = 4,
+    TILE_F32_64x64 = 5,
+    TILE_F32_32x32 = 6,            // one wave
+    // fp32 MFMA, 1x1 operands straight from global memory: direct (pw_mfma_kernel, the tile of one wave)
+    // and split-K over the 4 | 8 waves of a workgroup (pw_splitk_kernel)
+    TILE_PW_64x64 = 10,
+    TILE_PW_128x32 = 11,
+    TILE_PW_32x64 = 12,
+    TILE_PW_SPLITK4_32x32 = 13,
+    TILE_PW_SPLITK4_32x64 = 14,
+    TILE_PW_64x32 = 15,
+    TILE_PW_SPLITK8_32x32 = 16,
+    TILE_PW_SPLITK8_32x64 = 17,
+    // bf16x6, 16-deep stages (conv_x6_kernel); _W8: 8 waves instead of 4
+    TILE_X6_64x64 = 21,
+    TILE_X6_128x64 = 22,
+    TILE_X6_128x128 = 23,
+    TILE_X6_256x128 = 24,
+    TILE_X6_128x64_W8 = 27,
+    TILE_X6_128x128_W8 = 28,
+    // bf16x6, 32-deep swizzled stages (conv_x6b_kernel); _PF2: two register stages, not the skewed pipeline
+    TILE_X6B_256x128 = 25,         // takes the pre-split input (CONV p x3)
     TILE_X6B_256x128_SPLITK = 26,  // the same, K in two halves accumulated with atomics into a zeroed y
     TILE_X6B_128x128 = 29,
-    TILE_X6B_64x128 = 31,
-    TILE_PW_STREAM_WAVE = 34,      // streaming 1x1, one column block per wave, next block prefetched
-    TILE_PW_STREAM_WAVE_NOPF = 35, // the same without the prefetch
-    TILE_X6B_128x64 = 38,
+    TILE_X6B_128x128_PF2 = 30,
+    TILE_X6B_64x128 = 31,          // two workgroups per CU
+    TILE_X6B_64x128_PF2 = 32,
+    TILE_X6B_128x64 = 38,          // Cout <= 64 layers
     TILE_X6B_128x256 = 39,         // one N tile for Cout = 256: each A panel read once
+    // fp32 MFMA, streaming 1x1 with the weights in registers (pw_stream_kernel)
+    TILE_PW_STREAM = 33,           // every column block in one wave
+    TILE_PW_STREAM_WAVE = 34,      // one column block per wave, next block prefetched
+    TILE_PW_STREAM_WAVE_NOPF = 35, // the same without the prefetch
 };
+// Family membership, by id (a new id belongs to no family until it is listed here).
+constexpr bool tile_is_pw(int t) {  // direct and split-K pointwise: need a 1x1 / stride-1 dense input
+    return t == TILE_PW_64x64 || t == TILE_PW_128x32 || t == TILE_PW_32x64 || t == TILE_PW_64x32 ||
+           t == TILE_PW_SPLITK4_32x32 || t == TILE_PW_SPLITK4_32x64 || t == TILE_PW_SPLITK8_32x32 ||
+           t == TILE_PW_SPLITK8_32x64;
+}
+constexpr bool tile_is_pw_stream(int t) {
+    return t == TILE_PW_STREAM || t == TILE_PW_STREAM_WAVE || t == TILE_PW_STREAM_WAVE_NOPF;
+}
+constexpr bool tile_needs_w3(int t) {  // bf16x6: reads the split weight planes (ConvParams::w3)
+    return t == TILE_X6_64x64 || t == TILE_X6_128x64 || t == TILE_X6_128x128 || t == TILE_X6_256x128 ||
+           t == TILE_X6_128x64_W8 || t == TILE_X6_128x128_W8 || t == TILE_X6B_256x128 ||
+           t == TILE_X6B_256x128_SPLITK || t == TILE_X6B_128x128 || t == TILE_X6B_128x128_PF2 ||
+           t == TILE_X6B_64x128 || t == TILE_X6B_64x128_PF2 || t == TILE_X6B_128x64 || t == TILE_X6B_128x256;
+}
+// The bf16x6 form of an automatically chosen LDS tile (taken when the split planes are present), or
+// the tile itself.
+constexpr int tile_x6_form(int t) {
+    return t == TILE_F32_128x64 ? TILE_X6_128x64
+         : t == TILE_F32_128x128 ? TILE_X6_128x128
+         : t == TILE_F32_256x128 ? TILE_X6_256x128 : t;
+}
+// An input transform (SE scale, GN scale and shift, ReLU on load) is fused into the A-operand load.
+inline bool has_in_transform(const ConvParams& p) { return p.in_scale || p.in_shift || p.in_relu; }
 int conv_prepare(ConvParams& p);
 int conv_resolve_tile(const ConvParams& p, int tile);
 int conv_launch(ConvParams p, int tile, hipStream_t s);

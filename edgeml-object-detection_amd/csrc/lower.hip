@@ -474,6 +474,10 @@ struct ConvArgs {
     bool in_relu = false;
     std::string name;
 };
+// has_in_transform(ConvParams) (kernels.hpp) of the record these arguments become
+static bool has_in_transform(const ConvArgs& a) {
+    return a.in_scale.kind != Ref::NONE || a.in_shift.kind != Ref::NONE || a.in_relu;
+}
 
 // One CONV record (rec::conv), its tile from the tuned table, with the MEMSET a split-K tile needs
 // in front of it and the pre-split scratch an input transform gets.
@@ -502,13 +506,15 @@ static void conv_op(Plan& P, const ConvArgs& a) {
     int64_t& tile = o.i[r::tile];
     if (!a.tile && P.opt.tuned) {
         auto it = tile_table().find(conv_key(o));
-        if (it != tile_table().end() && it->second && (w3 || it->second < 20)) tile = it->second;
+        // (the stream tiles read no split planes, but were tuned against the bf16x6 tiles: taken only beside them)
+        const auto with_w3 = [](int t) { return tile_needs_w3(t) || tile_is_pw_stream(t); };
+        if (it != tile_table().end() && it->second && (w3 || !with_w3(it->second))) tile = it->second;
     }
     // the Cout = 256 layers the table puts on 256 x 128 run the 128 x 256 tile: one N tile, so each A
     // panel is read once (FRCNN 362.6 / 362.5 -> 369.9 / 373.8 img/s in alternated runs; box head 3x3
     // 2.09 -> 1.88 ms in the conv microbench, profiles/r4c_conv39.txt); input-transformed layers keep
     // 256 x 128 and its pre-split input (below)
-    const bool xf = a.in_scale.kind != Ref::NONE || a.in_shift.kind != Ref::NONE || a.in_relu;
+    const bool xf = has_in_transform(a);
     if (tile == TILE_X6B_256x128 && a.cout == 256 && !xf) tile = TILE_X6B_128x256;
     if (tile == TILE_X6B_256x128_SPLITK) {  // split K accumulates into a zeroed y: only where that is the whole store
         const bool dense = yp == a.cout && a.y_off == 0 && (a.y_bstride < 0 || a.y_bstride == Ho * Wo * a.cout);

@@ -1,14 +1,19 @@
-"""Did a change to the estimator sources change their gfx950 code?  Compiles svr, regress, kpredict, baseline
-and gbr.hip of two csrc directories under build.py's flags and compares every kernel.
+"""Did a change to csrc sources change their gfx950 code?  Compiles the named files (default: svr, regress,
+kpredict, baseline and gbr.hip, the estimators) of two csrc directories under build.py's flags and compares
+every kernel.
 
-    python tools/kernel_isa_diff.py PARENT_CSRC [CSRC]      (default: the tree's csrc; PARENT_CSRC inside a
-                                                             checkout, e.g. a `git worktree add` of the parent)
+    python tools/kernel_isa_diff.py PARENT_CSRC [CSRC] [--files conv.hip lower.hip]
+                                    (CSRC default: the tree's csrc; PARENT_CSRC inside a checkout, e.g. a
+                                     `git worktree add` of the parent)
 
 Per kernel: instruction text identical / mnemonic sequence identical / the compiler's register, scratch, LDS and
-occupancy figures equal.  A kernel whose mnemonics differ is printed with the diff of the two sequences and
-whether its float64 arithmetic (v_*_f64, v_mfma_f64*, v_exp*, v_rcp*, v_div*) still runs in the same order.
+occupancy figures equal.  A kernel whose mnemonics differ is printed with its instruction-count difference,
+whether the two sequences are the same multiset (a reordering only), the diff of the two sequences and whether
+its float64 arithmetic (v_*_f64, v_mfma_f64*, v_exp*, v_rcp*, v_div*) still runs in the same order.
 Exit status 1 when a kernel's mnemonics or figures differ.
 """
+import argparse
+import collections
 import difflib
 import os
 import re
@@ -33,10 +38,14 @@ def figures(meta):
 
 
 def main():
-    parent = sys.argv[1]
-    tree = sys.argv[2] if len(sys.argv) > 2 else os.path.join(S.PKG, "csrc")
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent")
+    ap.add_argument("tree", nargs="?", default=os.path.join(S.PKG, "csrc"))
+    ap.add_argument("--files", nargs="+", default=FILES)
+    args = ap.parse_args()
+    parent, tree = args.parent, args.tree
     bad = 0
-    for f in FILES:
+    for f in args.files:
         a, b = kernels(os.path.join(parent, f)), kernels(os.path.join(tree, f))
         print(f"{f}: {len(a)} kernels in the parent, {len(b)} in the tree")
         bad += set(a) != set(b)
@@ -52,6 +61,8 @@ def main():
                 print("    parent figures: " + " ".join(f"{k} {v}" for k, v in fa.items()))
             if oa != ob:
                 same = [o for o in oa if F64.match(o)] == [o for o in ob if F64.match(o)]
+                print(f"    {len(ob) - len(oa):+d} instructions, "
+                      f"{'a reordering only (same multiset)' if collections.Counter(oa) == collections.Counter(ob) else 'NOT the same multiset'}")
                 print(f"    float64 arithmetic mnemonics in {'unchanged' if same else 'CHANGED'} order; mnemonic diff:")
                 for ln in difflib.unified_diff(oa, ob, "parent", "tree", lineterm="", n=2):
                     print("      " + ln)
