@@ -32,6 +32,7 @@
 
 #include "fold_math.hpp"
 #include "kernels.hpp"
+#include "tree_math.hpp"
 
 namespace edgedet {
 
@@ -41,13 +42,8 @@ constexpr int GBR_SCAN_NT = 64 * GBR_SCAN_W;
 constexpr int GBR_NODES = 8;      // live nodes of one scanned level: depth <= 4
 constexpr int GBR_MAXDEPTH = 4;
 constexpr int GBR_PRED_STAGES = 1024;
-constexpr int GBR_QMIN = 26, GBR_QMAX = 1000;
+constexpr int GBR_QMIN = TREE_QMIN, GBR_QMAX = TREE_QMAX;
 constexpr uint8_t GBR_DEAD = 255;  // a training row that sits in a finished leaf
-
-typedef unsigned long long gu64;
-typedef unsigned __int128 gu128;
-
-__device__ __forceinline__ int gbr_ceil_log2(int64_t n) { return n <= 1 ? 0 : 64 - __clzll((gu64)(n - 1)); }
 
 // ------------------------------------------------------------------------------------ standardise
 __global__ void __launch_bounds__(GBR_NT) gbr_prepare_kernel(const double* __restrict__ x, int64_t N, int D,
@@ -65,27 +61,10 @@ __global__ void __launch_bounds__(GBR_NT) gbr_prepare_kernel(const double* __res
 // The 128-bit square goes in as four 32-bit limbs, each into a 64-bit accumulator (fewer than 2^31 rows).
 __device__ __forceinline__ void gbr_acc(gu64* sS, gu64* sQ, int* sc, int m, int64_t r) {
     if (sS) atomicAdd(&sS[m], (gu64)r);
-    const gu64 a = r < 0 ? 0ull - (gu64)r : (gu64)r;
-    const gu64 lo = a * a, hi = __umul64hi(a, a);
-    atomicAdd(&sQ[m * 4 + 0], lo & 0xffffffffull);
-    atomicAdd(&sQ[m * 4 + 1], lo >> 32);
-    atomicAdd(&sQ[m * 4 + 2], hi & 0xffffffffull);
-    atomicAdd(&sQ[m * 4 + 3], hi >> 32);
+    gu64 limb[4];
+    tree_sq_limbs(r, limb);
+    for (int i = 0; i < 4; ++i) atomicAdd(&sQ[m * 4 + i], limb[i]);
     if (sc) atomicAdd(&sc[m], 1);
-}
-
-// sklearn's impurity <= EPSILON (2^-52) on the integers: n Q - S^2 <= n^2 2^(2q - 52).  Q < 2^(124 - log2 n)
-// and |S| < 2^62 while no residual overflowed, so both sides fit 128 bits or the right one exceeds 2^124.
-__device__ __forceinline__ bool gbr_pure(int cnt, int64_t S, const gu64* Q4, int q) {
-    const gu128 Q = ((gu128)Q4[3] << 96) + ((gu128)Q4[2] << 64) + ((gu128)Q4[1] << 32) + (gu128)Q4[0];
-    const gu64 s = S < 0 ? 0ull - (gu64)S : (gu64)S;
-    const gu128 lhs = Q * (gu128)(gu64)cnt - (gu128)s * (gu128)s;
-    const gu64 n2 = (gu64)cnt * (gu64)cnt;
-    int sh = 2 * q - 52;
-    if (sh < 0) sh = 0;  // q >= 26 is checked on the host
-    const int bits = 64 - __clzll(n2);
-    if (sh + bits > 126) return true;
-    return lhs <= ((gu128)n2 << sh);
 }
 
 __global__ void __launch_bounds__(GBR_NT) gbr_stats_kernel(int nn, const int64_t* __restrict__ tr_off, int64_t n1,
@@ -366,7 +345,7 @@ __global__ void __launch_bounds__(GBR_NT) gbr_select_kernel(int level, int D, in
         const int ties = rc[0] + rc[1] + rc[2] + rc[3];
         if (tid == 0) {
             const bool found = cnt >= 2 && g >= 0.0;
-            const bool leaf = !found || gbr_pure(cnt, S, stQ + (f * GBR_NODES + m) * 4, q);
+            const bool leaf = !found || tree_pure(cnt, S, stQ + (f * GBR_NODES + m) * 4, q);
             const bool split = !leaf;
             const double thr = found ? cthr[c + j] : 0.0;
             const int wl = found ? cwl[c + j] : 0;
@@ -478,7 +457,7 @@ __global__ void __launch_bounds__(GBR_NT) gbr_update_kernel(int stage, int depth
         if (p >= 0 && p < n) {
             const double r = y[(int64_t)f * N + row] - Fn;
             const double t = r * ldexp(1.0, qv[f]);
-            const int64_t lim = (int64_t)1 << (62 - gbr_ceil_log2(n));
+            const int64_t lim = (int64_t)1 << (62 - tree_ceil_log2(n));
             bool bad = !(fabs(t) < 9.0e18);
             int64_t v = bad ? 0 : __double2ll_rn(t);
             bad = bad || v >= lim || v <= -lim;

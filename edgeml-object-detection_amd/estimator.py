@@ -29,9 +29,9 @@ stream (tests/test_gpu_estimator.py).
 KNeighborsRegressor (behind fit_model's StandardScaler, float64) through edgeml_amd.regress
 (csrc/regress.hip): estimate<k>.npz goes to <save_dir> itself (regression.py:447-448) and,
 with --model-dir, wts<k>.pickle holds plain numpy data instead of sklearn objects.  SVR and LSVR have a
-module and CLI of their own, edgeml_amd.svr, and so has GBR, edgeml_amd.gbr (§6e); what the
-three CLIs share lives here: base_parser, load_inputs, fold_targets, report_folds.  SGD, RFR
-(random streams) and the hidden-layer feature maps of the external YOLOv5 (stages 0-23) are out of scope
+module and CLI of their own, edgeml_amd.svr, and so have GBR, edgeml_amd.gbr (§6e), and RFR,
+edgeml_amd.rfr (§6f); what the four CLIs share lives here: base_parser, load_inputs, fold_targets, report_folds.
+SGD (a sequential per-sample update) and the hidden-layer feature maps of the external YOLOv5 (stages 0-23) are out of scope
 (DESIGN.md §7); this CLI exits naming what it builds.
 """
 import argparse
@@ -244,11 +244,12 @@ def check_model(opts):
         raise SystemExit(f"edgeml_amd.estimator runs regression.py on the stage-24 output features ({built}, "
                          "--stage 24); the YOLOv5 hidden-layer maps of stages 0-23 have no producer here")
     if opts.model != "CNN" and opts.model not in REGRESSORS:
-        why = ("SGD and RFR draw random streams that cannot be reproduced, SVR and LSVR need the libsvm / "
-               "liblinear dual solvers, GBR a tree builder" if opts.model in NOT_BUILT
+        why = ("SGD is a sequential per-sample update, SVR and LSVR need the libsvm / liblinear dual solvers, "
+               "GBR and RFR a tree builder" if opts.model in NOT_BUILT
                else f"'{opts.model}' is no model of regression.py")
         also = ".  python -m edgeml_amd.svr fits SVR and LSVR" if opts.model in ("SVR", "LSVR") else (
-            ".  python -m edgeml_amd.gbr fits GBR" if opts.model == "GBR" else "")
+            ".  python -m edgeml_amd.gbr fits GBR" if opts.model == "GBR" else (
+                ".  python -m edgeml_amd.rfr fits RFR" if opts.model == "RFR" else ""))
         raise SystemExit(f"edgeml_amd.estimator builds {built} on the stage-24 output features; {why}: "
                          f"--model {opts.model} is not built{also}")
 

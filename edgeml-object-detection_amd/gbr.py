@@ -227,7 +227,8 @@ def model_data(info, fold):
 def main(opts):
     if opts.model not in FITS:
         raise SystemExit(f"edgeml_amd.gbr builds --model GBR (Gradient Boosting Regressor); --model {opts.model} "
-                         f"belongs to edgeml_amd.estimator or edgeml_amd.svr, and RFR and SGD are not built (DESIGN.md §7)")
+                         f"belongs to edgeml_amd.estimator, edgeml_amd.svr or edgeml_amd.rfr, and SGD is not built "
+                         f"(DESIGN.md §7)")
     if opts.stage != 24:
         raise SystemExit("edgeml_amd.gbr runs on the stage-24 output features (--stage 24)")
     fit_opts = GBROpt(learning_rate=opts.learning_rate, n_estimators=opts.n_estimators, max_depth=opts.max_depth)

@@ -14,7 +14,8 @@ layer widths are read from the weight shapes), or the wts<fold>.pickle of `edgem
 support vectors and their dual coefficients) or of `edgeml_amd.estimator --model KNR` (the fold's training
 rows and targets): those two predict from their stored rows through edgeml_amd.kpredict
 (csrc/kpredict.hip), or the wts<fold>.pickle of `edgeml_amd.gbr --model GBR` (the boosted trees), which predicts
-through edgeml_amd.gbr.GBRModel (csrc/gbr.hip).  A KNR file written before the training rows were stored is
+through edgeml_amd.gbr.GBRModel (csrc/gbr.hip), or the wts<fold>.pickle of `edgeml_amd.rfr --model RFR` (the
+forest), which predicts through edgeml_amd.rfr.RFRModel (csrc/rfr.hip).  A KNR file written before the training rows were stored is
 refused.  The threshold is
 --threshold, or test.py:35 on EST_DIR/estimate<fold>.npz: train_est[argsort(-train_est)[int((len - 1) * R)]].
 
@@ -47,14 +48,15 @@ from . import fmt, ops
 
 
 # ---------------------------------------------------------------------------------------- estimator file
-MODEL_KINDS = ("svr", "knr", "gbr")  # an Estimator.model (kpredict.KernelModel, gbr.GBRModel) predicts these
+MODEL_KINDS = ("svr", "knr", "gbr", "rfr")  # an Estimator.model (kpredict.KernelModel, gbr.GBRModel, rfr.RFRModel)
+TREE_KINDS = ("gbr", "rfr")                 # ... of which these need no workspace
 
 
 class Estimator:
     """A trained reward estimator on `width` stage-24 features: kind "linear" (mean, scale, coef
     float64 [width], intercept), "mlp" (dims, state float32 in estimator.MlpSpec's layout), or "svr" /
     "knr" (model: the kpredict.KernelModel that predicts from the file's stored rows), or "gbr" (model: the
-    gbr.GBRModel that walks the file's trees)."""
+    gbr.GBRModel that walks the file's trees), or "rfr" (model: the rfr.RFRModel that walks the file's forest)."""
 
     def __init__(self, kind, width, **data):
         self.kind, self.width = kind, int(width)
@@ -89,7 +91,7 @@ class Estimator:
         d = self.device_data(feat.device)
         if self.kind in MODEL_KINDS:
             ws = scratch[2] if len(scratch) > 2 else None
-            if ws is None and self.kind != "gbr":  # edgedet_gbr_model_predict needs no workspace
+            if ws is None and self.kind not in TREE_KINDS:  # the tree walks need no workspace
                 raise ValueError(f"the {self.kind} estimator needs its workspace as scratch[2]")
             d["model"].predict_into(feat, est, ws, stream=stream)
             ops.check(ops.lib().edgedet_offload_flag(ops._ptr(est), B, float(threshold), ops._ptr(flag),
@@ -116,10 +118,10 @@ def load_estimator(path, width, support=False):
     """The estimator of a wts<fold>.pickle / wts<fold>.pth file (an LSVR file of edgeml_amd.svr is a linear
     model).  A KNR file that holds its training rows ('train', 'target') loads as kind "knr"; with
     support=True (what the cascade passes) an SVR file loads as kind "svr", otherwise it is refused as before;
-    a GBR file of edgeml_amd.gbr loads as kind "gbr".
+    a GBR file of edgeml_amd.gbr loads as kind "gbr", an RFR file of edgeml_amd.rfr as kind "rfr".
     Raises ValueError on a KNR file without training rows, on a file that is none of these, on inconsistent
     shapes, and when the model's feature width is not `width`."""
-    from . import gbr, kpredict
+    from . import gbr, kpredict, rfr
     from .estimator import MlpSpec
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
@@ -146,8 +148,8 @@ def load_estimator(path, width, support=False):
     if m.get("model") == "SVR" and not support:
         raise ValueError(f"{path}: an SVR file holds support vectors, and the cascade does not predict from them "
                          f"yet; train --model LSVR, LR, EN, BR or CNN")
-    if m.get("model") in ("GBR", "SVR") or (m.get("model") == "KNR" and "train" in m and "target" in m):
-        model = (gbr if m["model"] == "GBR" else kpredict).load(m)
+    if m.get("model") in ("GBR", "RFR", "SVR") or (m.get("model") == "KNR" and "train" in m and "target" in m):
+        model = {"GBR": gbr, "RFR": rfr}.get(m["model"], kpredict).load(m)
         _check_width(path, "model", model.width, width)
         return Estimator(model.kind, width, model=model)
     if m.get("model") == "KNR" or "coef" not in m:
@@ -434,7 +436,7 @@ def getargs(argv=None):
     a = argparse.ArgumentParser(prog="edgeml_amd.offload")
     a.add_argument("img_dir", help="Directory of the images to run the cascade on.")
     a.add_argument("save_dir", help="Directory for the detections (<name>.npy) and offload.npz.")
-    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR / LSVR / SVR / KNR / GBR) or wts<fold>.pth (CNN).")
+    a.add_argument("--estimator", required=True, help="wts<fold>.pickle (LR / EN / BR / LSVR / SVR / KNR / GBR / RFR) or wts<fold>.pth (CNN).")
     a.add_argument("--ratio", type=float, default=None, help="Offloading ratio: the threshold is test.py:35's on --estimates.")
     a.add_argument("--estimates", type=str, default=None, help="Directory holding estimate<fold>.npz (with --ratio).")
     a.add_argument("--threshold", type=float, default=None, help="Offload an image when its estimate exceeds this.")

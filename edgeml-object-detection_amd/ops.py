@@ -66,6 +66,8 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_knn_model_predict",
            "edgedet_gbr_workspace_size", "edgedet_gbr_prepare", "edgedet_gbr_fit", "edgedet_gbr_model_predict",
            "edgedet_gbr_best_split",
+           "edgedet_rfr_node_cap", "edgedet_rfr_workspace_size", "edgedet_rfr_best_split_workspace_size",
+           "edgedet_rfr_fit", "edgedet_rfr_best_split", "edgedet_rfr_model_predict",
            "edgedet_model_weights_size", "edgedet_model_pack", "edgedet_model_workspace_size", "edgedet_model_prepare",
            "edgedet_model_prepare_host", "edgedet_model_forward", "edgedet_model_max_detections",
            "edgedet_model_records", "edgedet_ssdlite_workspace_size", "edgedet_ssdlite_forward",
@@ -203,6 +205,19 @@ def lib():
     L.edgedet_gbr_model_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _i32, _i32, _vp,
                                             _vp]
     for name in ("edgedet_gbr_prepare", "edgedet_gbr_fit", "edgedet_gbr_best_split", "edgedet_gbr_model_predict"):
+        getattr(L, name).restype = ctypes.c_int
+    L.edgedet_rfr_node_cap.argtypes = [_i64, _i32]
+    L.edgedet_rfr_workspace_size.argtypes = [_vp, _i32, _i64, _i32, _i32, _i32, _i32]
+    L.edgedet_rfr_best_split_workspace_size.argtypes = [_i64, _i64, _i32, _i32]
+    for name in ("edgedet_rfr_node_cap", "edgedet_rfr_workspace_size", "edgedet_rfr_best_split_workspace_size"):
+        getattr(L, name).restype = _i64
+    L.edgedet_rfr_fit.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                  _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]
+    L.edgedet_rfr_best_split.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_rfr_model_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp]
+    for name in ("edgedet_rfr_fit", "edgedet_rfr_best_split", "edgedet_rfr_model_predict"):
         getattr(L, name).restype = ctypes.c_int
     _u64 = ctypes.c_uint64
     L.edgedet_model_weights_size.argtypes = [_i32, _i32, _i32]

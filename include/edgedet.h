@@ -606,6 +606,62 @@ int edgedet_gbr_model_predict(const double* feat, int64_t B, int64_t D, const do
                               const int16_t* feature, const double* threshold, const double* value, double init,
                               double learning_rate, int32_t T, int32_t depth, double* est, void* stream);
 
+/* ------------------------------------------------------------------ random forest regressor (regression.py) */
+/*
+ * regression.py's RandomForestRegressor(n_estimators, max_depth, min_samples_split) at sklearn's defaults
+ * (bootstrap on, every feature tried at every node) behind fit_model's StandardScaler, every tree of every
+ * cross-validation fold in flight (csrc/rfr.hip).  The bootstrap of a tree is given as integer row
+ * weights w (a row with w = 0 does not exist for that tree), the targets as integers yq = rint((y - F0) 2^q), so
+ * every weighted sum is exact and a split's gain does not depend on the order of summation; among bit-equal
+ * gains the lowest feature wins, then the lowest threshold.  The caller owns every buffer; the launchers
+ * allocate nothing, do not synchronise and return -1 with edgedet_last_error set on a bad argument.
+ *
+ * x, N, D, tr_idx, tr_off_host, tr_off, folds, mean, scale are the estimator regressors' (every fold non-empty,
+ * 1 <= D <= 255); z32, ord and sorted are edgedet_gbr_fit's.  Trees are stored as padded arrays [F][T][cap],
+ * cap = edgedet_rfr_node_cap(the largest fold's rows, max_depth) = min(2^(max_depth+1) - 1, 2 n - 1), the nodes
+ * numbered breadth first (the children of the split nodes of a level get consecutive ids in parent order, left
+ * then right): feature int16 (-1 = leaf or unused), threshold, left int32 (the right child is left + 1; -1 = leaf
+ * or unused), value (F0 + (S / W) 2^-q of the node's rows), n_node_samples (in-bag rows); a row goes right when
+ * double(z32) > threshold.
+ *
+ * edgedet_rfr_workspace_size: bytes of the workspace of edgedet_rfr_fit; < 0 on bad sizes.  groups (1..16) is
+ * the number of workgroups that share the features of one tree in a scan; no result depends on it.
+ * edgedet_rfr_best_split_workspace_size: the same for edgedet_rfr_best_split.  Workspaces are 8-byte aligned.
+ */
+int64_t edgedet_rfr_node_cap(int64_t n, int32_t max_depth);
+int64_t edgedet_rfr_workspace_size(const int64_t* tr_off_host, int32_t folds, int64_t D, int32_t T, int32_t max_depth,
+                                   int32_t min_samples_split, int32_t groups);
+int64_t edgedet_rfr_best_split_workspace_size(int64_t n, int64_t D, int32_t nn, int32_t groups);
+/* The whole fit, enqueued without a host round trip: one root launch, then one scan launch and one select launch
+ * per level (a finished tree's workgroups return at once), then one predict launch per fold.  w holds per fold f
+ * (at tr_off[f] * T) and tree t (at t * n_f) the weight of every training position; yq (at tr_off[f]) the
+ * targets' quanta, |yq| < 2^(62 - ceil(log2 n_f)); init [F] = F0; q [F] (host and device), 26 <= q <= 1000.  est
+ * [F][N] = the sum of a row's leaf values in tree order, divided by T; node_count [F][T]; tied [F] the split nodes
+ * with a second feature at the maximal gain; status [F] stays 0 (read it once, after the stream has drained). */
+int edgedet_rfr_fit(const float* z32, int64_t N, int64_t D, const double* x, const double* mean, const double* scale,
+                    const int32_t* tr_idx, const int32_t* ord, const float* sorted, const int64_t* tr_off_host,
+                    const int64_t* tr_off, int32_t folds, const double* init, const int32_t* q_host, const int32_t* q,
+                    const uint8_t* w, const int64_t* yq, int32_t T, int32_t max_depth, int32_t min_samples_split,
+                    int32_t groups, void* ws, int64_t ws_bytes, int16_t* feature, double* threshold, int32_t* left,
+                    double* value, int32_t* n_node_samples, int32_t* node_count, int32_t* tied, int32_t* status,
+                    double* est, void* stream);
+/* One level's scan and arg-best of one tree, for a given map slot [n] of training positions to nodes (a value
+ * outside 0..nn-1: in no node), weights w [n] and quanta yq [n]: per node m < nn its in-bag rows cnt, weighted
+ * count W and sum S, the best candidate's feature (-1: no valid candidate), threshold, gain, left weighted count
+ * wl, left rows cl and left sum Sl, leaf (1 when sklearn's rules other than the depth limit make the node a leaf)
+ * and tied (a second feature attains the gain). */
+int edgedet_rfr_best_split(const int32_t* ord, const float* sorted, int64_t n, int64_t D, const int32_t* slot,
+                           const uint8_t* w, const int64_t* yq, int32_t nn, int32_t q, int32_t min_samples_split,
+                           int32_t groups, void* ws, int64_t ws_bytes, int32_t* cnt, int32_t* W, int64_t* S,
+                           int32_t* feature, double* threshold, double* gain, int32_t* wl, int32_t* cl, int64_t* Sl,
+                           int32_t* leaf, int32_t* tied, void* stream);
+/* est [B] of one fold's forest (arrays [T][cap]) on the rows of feat [B][D], standardised as edgedet_gbr_prepare
+ * does: one thread per (row, tree) walks the tree, one thread per row adds the leaf values in tree order and
+ * divides by T, so the estimate equals the fit's bit for bit and does not depend on B. */
+int edgedet_rfr_model_predict(const double* feat, int64_t B, int64_t D, const double* mean, const double* scale,
+                              const int16_t* feature, const double* threshold, const int32_t* left,
+                              const double* value, int32_t T, int64_t cap, double* est, void* stream);
+
 /* ------------------------------------------------------------------ offloading cascade (csrc/offload.hip) */
 /*
  * The on-device decision chain between the weak and the strong detector (edgeml_amd.offload); every
