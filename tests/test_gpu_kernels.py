@@ -435,7 +435,9 @@ def test_conv_bf16x6_se_scale(tile):
 @pytest.mark.parametrize("shape", [(2, 25, 25, 256, 256, 3), (1, 13, 13, 1024, 512, 1), (1, 50, 50, 64, 128, 7)])
 def test_conv_bf16x6_is_fp32_grade(shape):
     """Against a float64 reference the bf16x6 conv errs no more than the exact-fp32 MFMA conv (x1.5):
-    the three dropped partial products sit below one fp32 rounding of each product."""
+    the three dropped partial products sit below one fp32 rounding of each product.
+    (Its yardstick, tile 3, is the engine's own least accurate kernel: test_gpu_conv_budget.py holds
+    every tile to torch's float32 CPU conv error against float64 instead.)"""
     from edgeml_amd import ops
     from edgeml_amd.plan import pack_conv_weight
     B, H, W, Cin, Cout, k = shape
