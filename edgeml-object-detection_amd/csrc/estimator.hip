@@ -17,6 +17,7 @@
 //     (dy - mean(dy) - xhat * mean(dy * xhat)) * gamma * invstd, Adam's lerp / addcmul / addcdiv
 //     with the bias corrections in double.
 // mlp_predict_kernel: eval-mode forward (running statistics, no dropout), one thread per row.
+#include "dropout_hash.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
@@ -86,18 +87,11 @@ struct MlpFitParams {
     uint64_t seed;
 };
 
-__device__ __forceinline__ uint32_t mlp_hash(uint64_t a, uint64_t b) {  // splitmix64 finalizer
-    uint64_t z = a * 0x9E3779B97F4A7C15ull + b + 0x632BE59BD9B4E019ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return (uint32_t)((z ^ (z >> 31)) >> 32);
-}
-
-// keep test of one dropout unit: u in [0, 1) with 24 bits; kept when u >= p (probability 1 - p)
+// keep test of one dropout unit (mlp_hash and hash_keep: dropout_hash.hpp, shared with convnet.hip)
 __device__ __forceinline__ bool mlp_keep(const MlpFitParams& p, int fold, int64_t step, int layer, int unit) {
     const uint32_t h = mlp_hash(p.seed ^ ((uint64_t)fold << 48), ((uint64_t)step << 20) ^ ((uint64_t)layer << 16) ^
                                                                      (uint64_t)unit);
-    return (float)(h >> 8) * (1.0f / 16777216.0f) >= p.dropout;
+    return hash_keep(h, p.dropout);
 }
 
 struct MlpSmem {

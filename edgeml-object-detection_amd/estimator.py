@@ -31,8 +31,8 @@ KNeighborsRegressor (behind fit_model's StandardScaler, float64) through edgeml_
 with --model-dir, wts<k>.pickle holds plain numpy data instead of sklearn objects.  SVR and LSVR have a
 module and CLI of their own, edgeml_amd.svr, and so have GBR, edgeml_amd.gbr (§6e), and RFR,
 edgeml_amd.rfr (§6f); what the four CLIs share lives here: base_parser, load_inputs, fold_targets, report_folds.
-SGD (a sequential per-sample update) and the hidden-layer feature maps of the external YOLOv5 (stages 0-23) are out of scope
-(DESIGN.md §7); this CLI exits naming what it builds.
+The hidden-layer feature maps of the external YOLOv5 (stages 0-23) train a conv net in edgeml_amd.convnet (§6g); SGD (a
+sequential per-sample update) is out of scope; this CLI exits naming what it builds.
 """
 import argparse
 import ctypes
@@ -242,7 +242,8 @@ def check_model(opts):
     built = "--model CNN, LR (Linear Regression), EN (Elastic Net), BR (Bayesian Ridge) or KNR (K-nearest Neighbors)"
     if opts.stage != 24:
         raise SystemExit(f"edgeml_amd.estimator runs regression.py on the stage-24 output features ({built}, "
-                         "--stage 24); the YOLOv5 hidden-layer maps of stages 0-23 have no producer here")
+                         "--stage 24); the YOLOv5 hidden-layer maps of stages 0-23 train a conv net: "
+                         "python -m edgeml_amd.convnet ... --stage N --channels ...")
     if opts.model != "CNN" and opts.model not in REGRESSORS:
         why = ("SGD is a sequential per-sample update, SVR and LSVR need the libsvm / liblinear dual solvers, "
                "GBR and RFR a tree builder" if opts.model in NOT_BUILT
@@ -268,12 +269,19 @@ def fold_targets(reward, split, normalize, dtype):
 def load_inputs(opts):
     """The three inputs of every regression CLI (regression.py:399-407): stage-24 features, reward, split."""
     features = load_stage24(opts.data_dir)
+    reward, split = load_reward_split(opts, len(features))
+    return features, reward, split
+
+
+def load_reward_split(opts, n_features):
+    """The reward and split halves of load_inputs, checked against the number of feature rows (edgeml_amd.convnet
+    loads feature maps instead of the stage-24 rows)."""
     with np.load(opts.reward_path, allow_pickle=False) as z:
         reward = z["reward"]
-    assert len(features) == len(reward), "Inconsistent number of feature maps and offloading rewards."
+    assert n_features == len(reward), "Inconsistent number of feature maps and offloading rewards."
     split = np.load(opts.split_path, allow_pickle=False)
     assert len(reward) == split.shape[1], "Inconsistent number of data points from the dataset and the split."
-    return features, reward, split
+    return reward, split
 
 
 def report_folds(opts, name, y, split, results, fold_model):

@@ -230,7 +230,8 @@ def main(opts):
                          f"belongs to edgeml_amd.estimator, edgeml_amd.svr or edgeml_amd.rfr, and SGD is not built "
                          f"(DESIGN.md §7)")
     if opts.stage != 24:
-        raise SystemExit("edgeml_amd.gbr runs on the stage-24 output features (--stage 24)")
+        raise SystemExit("edgeml_amd.gbr runs on the stage-24 output features (--stage 24); the hidden-layer "
+                         "feature maps of stages 0-23 train a conv net: python -m edgeml_amd.convnet")
     fit_opts = GBROpt(learning_rate=opts.learning_rate, n_estimators=opts.n_estimators, max_depth=opts.max_depth)
     try:
         check_opts(fit_opts)

@@ -126,6 +126,10 @@ def load_estimator(path, width, support=False):
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
         named = {k: v.numpy() for k, v in named.items() if torch.is_tensor(v)}
+        if any(k.startswith("conv_stacks.") for k in named):
+            raise ValueError(f"{path}: a conv-stack estimator of edgeml_amd.convnet (conv_stacks.* tensors): it reads the "
+                             "weak detector's hidden-layer feature maps, which the cascade does not have; use an "
+                             "estimator trained on the stage-24 output features")
         L = 0
         while f"linear_stacks.{L}.0.weight" in named:
             L += 1

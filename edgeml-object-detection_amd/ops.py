@@ -53,6 +53,10 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_split_bf16x3", "edgedet_conv_tile", "edgedet_box_correct", "edgedet_orie_ap",
            "edgedet_map_eval", "edgedet_output_features", "edgedet_conv2d_x3", "edgedet_ssd_stem",
            "edgedet_mlp_state_size", "edgedet_mlp_fit", "edgedet_mlp_predict",
+           "edgedet_cnn_wgrad", "edgedet_cnn_repack", "edgedet_cnn_bn_stats", "edgedet_cnn_col_reduce",
+           "edgedet_cnn_act_fwd", "edgedet_cnn_act_bwd", "edgedet_cnn_maxpool_fwd", "edgedet_cnn_maxpool_bwd",
+           "edgedet_cnn_gmean_fwd", "edgedet_cnn_gmean_bwd", "edgedet_cnn_linear_fwd", "edgedet_cnn_linear_dx",
+           "edgedet_cnn_loss", "edgedet_cnn_adam",
            "edgedet_dcsb_fit", "edgedet_svm_workspace_size", "edgedet_svm_fit", "edgedet_svm_hessian",
            "edgedet_svm_decision",
            "edgedet_reg_workspace_size", "edgedet_reg_scaler", "edgedet_reg_gram", "edgedet_reg_eigh",
@@ -142,6 +146,25 @@ def lib():
                                   _vp, _i32, _i32, ctypes.c_float, ctypes.c_float, _vp, _i32, ctypes.c_float, _i32,
                                   ctypes.c_float, ctypes.c_uint64, _vp]
     L.edgedet_mlp_predict.argtypes = [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]
+    # the conv-stack estimator's step kernels (csrc/convnet.hip)
+    L.edgedet_cnn_wgrad.argtypes = [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp]
+    L.edgedet_cnn_repack.argtypes = [_vp, _i64, _i64, _i32, _vp, _vp, _vp]
+    L.edgedet_cnn_bn_stats.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_cnn_col_reduce.argtypes = [_vp, _vp, _vp, _i64, _i64, _flt, _vp, _vp, _vp]
+    L.edgedet_cnn_act_fwd.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _flt, ctypes.c_uint64,
+                                      ctypes.c_uint64, _vp, _vp, _vp]
+    L.edgedet_cnn_act_bwd.argtypes = [_vp, _vp, _vp, _i64, _i64, _flt, _vp, _vp, _vp, _vp, _i32, _vp, _vp]
+    L.edgedet_cnn_maxpool_fwd.argtypes = [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]
+    L.edgedet_cnn_maxpool_bwd.argtypes = [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]
+    L.edgedet_cnn_gmean_fwd.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp]
+    L.edgedet_cnn_gmean_bwd.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp]
+    L.edgedet_cnn_linear_fwd.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
+    L.edgedet_cnn_linear_dx.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp, _vp]
+    L.edgedet_cnn_loss.argtypes = [_vp, _vp, _i64, _i32, _vp, _vp, _vp]
+    L.edgedet_cnn_adam.argtypes = [_vp, _vp, _vp, _vp, _i64, _flt, _flt, _flt, _vp]
+    for name in EXPORTS:
+        if name.startswith("edgedet_cnn_"):
+            getattr(L, name).restype = ctypes.c_int
     L.edgedet_dcsb_fit.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]
     L.edgedet_svm_workspace_size.argtypes = [_i32, _i64, _i64]

@@ -269,7 +269,8 @@ def main(opts):
                          f"to edgeml_amd.estimator, edgeml_amd.svr or edgeml_amd.gbr, and SGD is not built "
                          f"(DESIGN.md §7)")
     if opts.stage != 24:
-        raise SystemExit("edgeml_amd.rfr runs on the stage-24 output features (--stage 24)")
+        raise SystemExit("edgeml_amd.rfr runs on the stage-24 output features (--stage 24); the hidden-layer "
+                         "feature maps of stages 0-23 train a conv net: python -m edgeml_amd.convnet")
     fit_opts = RFROpt(n_estimators=opts.n_estimators, max_depth=opts.max_depth,
                       min_samples_split=opts.min_samples_split)
     try:

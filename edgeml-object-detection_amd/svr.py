@@ -167,7 +167,8 @@ def main(opts):
         raise SystemExit(f"edgeml_amd.svr builds --model SVR (Support Vector Regression, rbf) and LSVR (Linear "
                          f"Support Vector Regression); --model {opts.model} belongs to edgeml_amd.estimator")
     if opts.stage != 24:
-        raise SystemExit("edgeml_amd.svr runs on the stage-24 output features (--stage 24)")
+        raise SystemExit("edgeml_amd.svr runs on the stage-24 output features (--stage 24); the hidden-layer "
+                         "feature maps of stages 0-23 train a conv net: python -m edgeml_amd.convnet")
     features, reward, split = estimator.load_inputs(opts)
     y = estimator.fold_targets(reward, split, opts.normalize, np.float64)
     fit_opts = None

@@ -739,6 +739,68 @@ int edgedet_jpeg_decode_batch(const void* packets, const int64_t* offsets, int32
                               int32_t max_blocks, void* planes, int64_t plane_stride, uint8_t* out, void* stream);
 int edgedet_jpeg_reconstruct_host(const void* host_packet, uint8_t* out);
 
+/* ------------------------------------------------- conv-stack estimator (csrc/convnet.hip) */
+/*
+ * The kernels of one training step of lib/nn_model.py EdgeDetectionNet with conv stacks
+ * (regression.py:242-355 fit_CNN on the hidden-layer feature maps; the host loop is edgeml_amd/convnet.py,
+ * DESIGN.md 6g).  Everything is NHWC: a map [B][H][W][C] and a batch [B][D] are both a matrix [M][C] of
+ * M rows (pixels or samples) by C channels.  The conv forward and data gradient are edgedet_conv2d_ex.
+ * No kernel uses atomics: every result is bit-identical from run to run.
+ *
+ * edgedet_cnn_wgrad: dw[co][kh][kw][ci] = sum_{b,h,w} dy[b][h][w][co] x[b][h+kh-k/2][w+kw-k/2][ci] (zero
+ *   outside the map) for a stride-1 'same' conv of odd size k, on v_mfma_f32_16x16x4_f32 with K = B*H*W
+ *   summed in stages of 64 pixels.  dw is dense [Cout][k*k*Cin] (no row padding).
+ * edgedet_cnn_repack: w [Cout][k][k][Cin] dense -> wf [Cout][edgedet_conv_weight_k(k, k, Cin)], the conv
+ *   engine's forward pack, and (wb non-null) wb [Cin][edgedet_conv_weight_k(k, k, Cout)] =
+ *   w[co][k-1-kh][k-1-kw][ci] at [ci][kh][kw][co], the pack whose conv over dy is the data gradient.
+ *   Only the weights are written: the caller zeroes the row pads once.
+ * edgedet_cnn_bn_stats: BatchNorm (1d or 2d) train statistics of z [M][C]: mean, invstd =
+ *   1 / sqrt(biased var + 1e-5), and running = 0.9 running + 0.1 (mean | unbiased var).
+ * edgedet_cnn_act_fwd: a = dropout(relu(gamma h + beta)); mode 0: h = z (no BatchNorm, gamma / beta unused);
+ *   mode 1: h = (z - mean) invstd; mode 2 (eval): mean / invstd point at the running mean / running VAR.
+ *   xhat (nullable) receives h.  Dropout (dropout > 0): element (row r = b HW + pix, channel c) is kept when
+ *   u >= dropout for u = the top 24 bits of splitmix64(key, step << 32 | ((b C + c) HW + pix)), i.e. the
+ *   counter is the element's NCHW flat index, independent of the device layout; kept values are scaled by
+ *   1 / (1 - dropout).  key = seed ^ fold << 48 ^ layer << 40 by convention (edgeml_amd/convnet.py).
+ * edgedet_cnn_col_reduce: a null: out0[c] = sum_r v[r][c] (a bias gradient).  a non-null: v is the
+ *   gradient behind ReLU + Dropout, dy = a > 0 ? v scale : 0; out0 = sum dy (dbeta), out1 = sum dy xhat (dgamma).
+ * edgedet_cnn_act_bwd: dz = bn ? (dy - sdy / M - xhat sdyx / M) invstd gamma : dy with dy as above.
+ * edgedet_cnn_maxpool_fwd / _bwd: MaxPool2d(2, 2), floor mode; idx [B][H/2][W/2][C] holds h W + w of the
+ *   first maximum in window order (torch's argmax); the backward routes dy to it, zero elsewhere.
+ * edgedet_cnn_gmean_fwd / _bwd: mean over the HW pixels of x [B][HW][C] and its gradient.
+ * edgedet_cnn_linear_fwd: z [B][dout] = x [B][din] w[dout][din]^T + bias; _dx: dx = dz w.
+ * edgedet_cnn_loss: loss[0] = mean (pred - y)^2 (times y when weighted); dpred (nullable) its gradient.
+ * edgedet_cnn_adam: torch.optim.Adam's single-tensor step over n parameters: step_size = lr / (1 - 0.9^t)
+ *   and bc2_sqrt = sqrt(1 - 0.999^t) computed by the caller in double.
+ */
+int edgedet_cnn_wgrad(const float* x, const float* dy, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                      int32_t k, float* dw, void* stream);
+int edgedet_cnn_repack(const float* w, int64_t Cout, int64_t Cin, int32_t k, float* wf, float* wb, void* stream);
+int edgedet_cnn_bn_stats(const float* z, int64_t M, int64_t C, float* running_mean, float* running_var, float* mean,
+                         float* invstd, void* stream);
+int edgedet_cnn_col_reduce(const float* v, const float* a, const float* xhat, int64_t M, int64_t C, float scale,
+                           float* out0, float* out1, void* stream);
+int edgedet_cnn_act_fwd(const float* z, int64_t M, int64_t C, int64_t HW, const float* gamma, const float* beta,
+                        const float* mean, const float* invstd, int32_t mode, float dropout, uint64_t key,
+                        uint64_t step, float* xhat, float* a, void* stream);
+int edgedet_cnn_act_bwd(const float* da, const float* a, const float* xhat, int64_t M, int64_t C, float scale,
+                        const float* gamma, const float* invstd, const float* sdy, const float* sdyx, int32_t bn,
+                        float* dz, void* stream);
+int edgedet_cnn_maxpool_fwd(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, float* y, int32_t* idx,
+                            void* stream);
+int edgedet_cnn_maxpool_bwd(const float* dy, const int32_t* idx, int64_t B, int64_t H, int64_t W, int64_t C,
+                            float* dx, void* stream);
+int edgedet_cnn_gmean_fwd(const float* x, int64_t B, int64_t HW, int64_t C, float* y, void* stream);
+int edgedet_cnn_gmean_bwd(const float* dy, int64_t B, int64_t HW, int64_t C, float* dx, void* stream);
+int edgedet_cnn_linear_fwd(const float* x, int64_t B, int64_t din, int64_t dout, const float* w, const float* bias,
+                           float* z, void* stream);
+int edgedet_cnn_linear_dx(const float* dz, int64_t B, int64_t din, int64_t dout, const float* w, float* dx,
+                          void* stream);
+int edgedet_cnn_loss(const float* pred, const float* y, int64_t n, int32_t weighted, float* loss, float* dpred,
+                     void* stream);
+int edgedet_cnn_adam(float* param, const float* grad, float* m, float* v, int64_t n, float step_size, float bc2_sqrt,
+                     float weight_decay, void* stream);
+
 /* --------------------------------------------------------------------------------- misc */
 const char* edgedet_last_error(void);
 /* Library/ABI version: (major << 16) | minor. */
