@@ -85,6 +85,57 @@ struct MbParams {
 };
 int mbconv_launch(const MbParams& p, hipStream_t s);
 
+// The kernel's geometry, shared by the kernel, its launcher and the lowering: one wave per MBW_C
+// expanded channels, a TH x TW output tile per workgroup, every LDS region sized here.
+constexpr int MBW_C = 16;               // expanded channels per wave
+constexpr int MBW_MAXW = 8;             // waves per workgroup (Cexp <= 128)
+constexpr int MBW_LDS_MAX = 160 * 1024; // the LDS of a CU
+constexpr int mbw_tile_h(int S) { return S == 1 ? 8 : 4; }
+constexpr int MBW_TILE_W = 8;
+
+template <int K, int S, int CINP, int TH, int TW>
+struct MbwGeom {
+    static constexpr int IHh = (TH - 1) * S + K, IWh = (TW - 1) * S + K;  // halo rows, columns
+    static constexpr int NPX = IHh * IWh, NPXP = (NPX + 15) / 16 * 16;
+    static constexpr int P = TH * TW;                                       // output pixels (16k)
+    static constexpr int XS = CINP + 1;                                     // odd pitches: spread banks
+    static constexpr int ES = MBW_C + 1;
+    static constexpr int PS = 33;                                           // partial sums: 32 + 1
+    static constexpr int EW = NPXP * ES > P * PS ? NPXP * ES : P * PS;      // per wave: chunk, then partials
+    static size_t smem(int nw) { return 4 * ((size_t)NPXP * (XS + 1) + (size_t)nw * (EW + P * ES)); }
+};
+
+// The padded input width of a block (the kernel's CINP) and its wave count: at least four waves (the
+// halo loader's stride); waves past Cexp carry zero weights.
+inline int mbw_cinp(int Cin) { return Cin <= 16 ? 16 : Cin <= 24 ? 24 : 32; }
+inline int mbw_waves(int Cexp) { return Cexp > 4 * MBW_C ? (int)cdiv(Cexp, MBW_C) : 4; }
+
+template <int K, int S>
+inline size_t mbw_lds_ks(int cinp, int nw) {
+    constexpr int TH = mbw_tile_h(S), TW = MBW_TILE_W;
+    return cinp == 16 ? MbwGeom<K, S, 16, TH, TW>::smem(nw)
+         : cinp == 24 ? MbwGeom<K, S, 24, TH, TW>::smem(nw)
+                      : MbwGeom<K, S, 32, TH, TW>::smem(nw);
+}
+
+// Dynamic LDS of the workgroup that runs such a block (K in {3, 5}, stride in {1, 2}).
+inline size_t mbconv_lds(int K, int stride, int Cin, int Cexp) {
+    const int cinp = mbw_cinp(Cin), nw = mbw_waves(Cexp);
+    return K == 3 ? (stride == 1 ? mbw_lds_ks<3, 1>(cinp, nw) : mbw_lds_ks<3, 2>(cinp, nw))
+                  : (stride == 1 ? mbw_lds_ks<5, 1>(cinp, nw) : mbw_lds_ks<5, 2>(cinp, nw));
+}
+
+// The blocks mbconv_launch takes; the lowering sends exactly these to an MBCONV record.  Every
+// geometry fits the LDS but K = 5, stride 2 with Cin > 24 and Cexp > 112 (169,728 bytes).
+constexpr const char* MBCONV_DOMAIN =
+    "mbconv: K in {3, 5}, stride in {1, 2}, Cin <= 32 (a multiple of 4), Cout <= 32, Cexp <= 128, and the "
+    "tile within 160 KiB of LDS (K = 5, stride 2, Cin > 24: Cexp <= 112)";
+inline bool mbconv_fits(int K, int stride, int Cin, int Cout, int Cexp) {
+    return (K == 3 || K == 5) && (stride == 1 || stride == 2) && Cin >= 1 && Cin <= 32 && Cin % 4 == 0 &&
+           Cout >= 1 && Cout <= 32 && Cexp >= 1 && Cexp <= MBW_C * MBW_MAXW &&
+           mbconv_lds(K, stride, Cin, Cexp) <= (size_t)MBW_LDS_MAX;
+}
+
 
 struct PoolParams {
     const float* x;

@@ -836,21 +836,8 @@ extern "C" int edgedet_ssd_stem(const float* x, int64_t B, int64_t H, int64_t W,
 //            LDS reads per output instead of 9), taps in (kh, kw) order, + bias, act; into LDS;
 //   project  v_mfma_f32_16x16x4_f32: [tile pixels] x [the wave's 16 channels] x [Cout <= 32];
 // then the waves' partial projections are added in wave order ((w0 + w1) + w2 ...), + bias (+ the
-// input pixel), and stored.  All weights live in registers, loaded before the halo.
-constexpr int MBW_C = 16;    // expanded channels per wave
-constexpr int MBW_MAXW = 8;  // waves per workgroup (Cexp <= 128)
-
-template <int K, int S, int CINP, int TH, int TW>
-struct MbwGeom {
-    static constexpr int IHh = (TH - 1) * S + K, IWh = (TW - 1) * S + K;  // halo rows, columns
-    static constexpr int NPX = IHh * IWh, NPXP = (NPX + 15) / 16 * 16;
-    static constexpr int P = TH * TW;                                       // output pixels (16k)
-    static constexpr int XS = CINP + 1;                                     // odd pitches: spread banks
-    static constexpr int ES = MBW_C + 1;
-    static constexpr int PS = 33;                                           // partial sums: 32 + 1
-    static constexpr int EW = NPXP * ES > P * PS ? NPXP * ES : P * PS;      // per wave: chunk, then partials
-    static size_t smem(int nw) { return 4 * ((size_t)NPXP * (XS + 1) + (size_t)nw * (EW + P * ES)); }
-};
+// input pixel), and stored.  All weights live in registers, loaded before the halo.  The geometry
+// (MbwGeom, MBW_C, MBW_MAXW) and the domain (mbconv_fits) are in kernels.hpp, shared with the lowering.
 
 // A workgroup barrier for LDS traffic only: __syncthreads' workgroup fence also waits for every
 // outstanding global load and store (vmcnt(0)), which would land the next tile's halo prefetch and the
@@ -1072,18 +1059,18 @@ static int mbw_set_lds(KF kernel, size_t bytes) {
 
 template <int K, int S, int ACT, int CINP>
 static int mbconv_launch_t(const MbParams& p, hipStream_t s) {
-    constexpr int TH = S == 1 ? 8 : 4, TW = 8;
+    constexpr int TH = mbw_tile_h(S), TW = MBW_TILE_W;
     using G = MbwGeom<K, S, CINP, TH, TW>;
-    // at least four waves (the halo loader's stride); waves past Cexp carry zero weights
-    const int nw = std::max(4, (int)cdiv(p.Cexp, MBW_C)), tiles_w = (int)cdiv(p.Wo, TW);
+    const int nw = mbw_waves(p.Cexp), tiles_w = (int)cdiv(p.Wo, TW);
     const int tiles_img = (int)cdiv(p.Ho, TH) * tiles_w, ntiles = p.B * tiles_img;
-    const size_t lds = G::smem(nw);
-    EDGEDET_REQUIRE(lds <= 160 * 1024, "mbconv: tile exceeds the LDS");
+    const size_t lds = G::smem(nw);  // mbconv_launch has checked mbconv_fits: within MBW_LDS_MAX
+    EDGEDET_REQUIRE(CINP == mbw_cinp(p.Cin) && lds == mbconv_lds(K, S, p.Cin, p.Cexp) && lds <= (size_t)MBW_LDS_MAX,
+                    "mbconv: the instantiation is not the one mbconv_fits sized");
     auto kern = mbconv_kernel<K, S, ACT, CINP, TH, TW>;
     if (int rc = mbw_set_lds(kern, lds)) return rc;
     // a resident grid (the workgroups that fit the CUs at once) looping over the tiles, each tile's
     // halo loaded under the previous tile's compute
-    const int per_cu = std::max(1, (int)((160 * 1024) / lds));
+    const int per_cu = std::max(1, (int)(MBW_LDS_MAX / lds));
     const int grid = std::min(ntiles, 256 * per_cu);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * nw), lds, s, p, tiles_w, tiles_img, ntiles);
     EDGEDET_LAUNCH_CHECK();
@@ -1092,8 +1079,9 @@ static int mbconv_launch_t(const MbParams& p, hipStream_t s) {
 
 template <int K, int S, int ACT>
 static int mbconv_launch_a(const MbParams& p, hipStream_t s) {
-    if (p.Cin <= 16) return mbconv_launch_t<K, S, ACT, 16>(p, s);
-    if (p.Cin <= 24) return mbconv_launch_t<K, S, ACT, 24>(p, s);
+    const int cinp = mbw_cinp(p.Cin);
+    if (cinp == 16) return mbconv_launch_t<K, S, ACT, 16>(p, s);
+    if (cinp == 24) return mbconv_launch_t<K, S, ACT, 24>(p, s);
     return mbconv_launch_t<K, S, ACT, 32>(p, s);
 }
 
@@ -1109,9 +1097,7 @@ static int mbconv_launch_ks(const MbParams& p, hipStream_t s) {
 
 int mbconv_launch(const MbParams& p, hipStream_t s) {
     EDGEDET_REQUIRE(p.x && p.w1 && p.b1 && p.wd && p.bd && p.w2 && p.b2 && p.y, "mbconv: null pointer");
-    EDGEDET_REQUIRE(p.Cin >= 1 && p.Cin <= 32 && p.Cin % 4 == 0 && p.Cout >= 1 && p.Cout <= 32 && p.Cexp >= 1 &&
-                        p.Cexp <= MBW_C * MBW_MAXW,
-                    "mbconv: Cin <= 32 (a multiple of 4), Cout <= 32, Cexp <= 128");
+    EDGEDET_REQUIRE(mbconv_fits(p.K, p.stride, p.Cin, p.Cout, p.Cexp), MBCONV_DOMAIN);
     EDGEDET_REQUIRE(((uintptr_t)p.x & 15) == 0, "mbconv: input 16-byte aligned");
     EDGEDET_REQUIRE(p.ld1 >= p.Cin && p.ld2 >= p.Cexp, "mbconv: weight row strides");
     EDGEDET_REQUIRE(p.pad == (p.K - 1) / 2 && p.Ho == (p.H + 2 * p.pad - p.K) / p.stride + 1 &&

@@ -14,23 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.fmaf32 import fma32
+
 DEV = "cuda"
 F32 = np.float32
-
-
-def fma32(a, b, c):
-    """fmaf(a, b, c) on float32 arrays with one rounding.  The product is exact in float64; the float64
-    sum is rounded to odd with its TwoSum residual, so the final rounding to float32 cannot double-round
-    across a float32 tie."""
-    a64, b64, c64 = (np.asarray(v, dtype=np.float64) for v in (a, b, c))
-    p = a64 * b64
-    s = p + c64
-    bb = s - p
-    err = (p - (s - bb)) + (c64 - bb)
-    even = (s.view(np.int64) & 1) == 0
-    fix = np.isfinite(s) & (err != 0) & even
-    s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
-    return s.astype(F32)
 
 
 def test_fma32_matches_libm_fmaf():
@@ -52,13 +39,17 @@ def test_fma32_matches_libm_fmaf():
     sg = rng.choice([-1.0, 1.0], n)
     at = (1.0 + sg * u).astype(F32)
     bt = (np.ldexp(1.0 - sg * u + u * u, e - 24) * rng.choice([-1.0, 1.0], n)).astype(F32)
-    a, b, c = np.concatenate([a, at]), np.concatenate([b, bt]), np.concatenate([c, ct])
+    # results in float32's subnormal range, whose midpoints are not the normal range's
+    an = (rng.standard_normal(n) * 1e-19).astype(F32)
+    bn = (rng.standard_normal(n) * 1e-20).astype(F32)
+    cn = (rng.standard_normal(n) * 1e-39).astype(F32)
+    a, b, c = np.concatenate([a, at, an]), np.concatenate([b, bt, bn]), np.concatenate([c, ct, cn])
     want = np.array([libm.fmaf(float(x), float(y), float(z)) for x, y, z in zip(a, b, c)], dtype=F32)
     got = fma32(a, b, c)
     assert np.array_equal(got.view(np.int32), want.view(np.int32))
     # the constructed half really needs the residual: plain float64 rounding gets some of them wrong
     plain = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F32)
-    assert (plain[n:].view(np.int32) != want[n:].view(np.int32)).any()
+    assert (plain[n:2 * n].view(np.int32) != want[n:2 * n].view(np.int32)).any()
 
 
 def _act(v, act):
