@@ -5,12 +5,16 @@ loop of regression.py:242-355 (fit_CNN).
 
     python -m edgeml_amd.convnet data_dir reward_path split_path save_dir --stage N [--resize S]
         --channels 64 32 [--kernels 3 3] [--pools 1 1] [--hidden 16 16 16 16]
-        [--normalize] [--weight] [--model-dir D] [--seed 0]
+        [--normalize] [--weight] [--model-dir D] [--seed 0] [--weak yolov5|ssd] [--epochs 100]
 
 Reads <data_dir>/<image>/stage{N}_{name}_features.npy ([C, h, w] maps written by the reference's YOLOv5
 scripts) in sorted directory order, the reward npz and the k-fold split, and writes estimate<k>.npz into
 <save_dir>_best and <save_dir>_last (and, with --model-dir, wts<k>.pth under EdgeDetectionNet's state-dict
 names), as edgeml_amd.estimator does for stage 24.
+
+--weak ssd reads the maps python -m edgeml_amd.maps wrote from SSDLite's backbone instead: the stage numbers and
+file-name tokens are those of the library's stage table (edgeml_amd.tapnet.stage_table, stages 1-20), and the
+trained file drives the cascade (python -m edgeml_amd.offload --stage N --resize S).
 
 --resize S > 0 pads every map square (zeros at the bottom or the right, lib/metrics.py roi_padding) and
 RoI-aligns it to S x S (lib/data.py load_feature: box [0, 0, w, h], scale 1, aligned=False, adaptive sampling)
@@ -491,10 +495,11 @@ def fit_folds(features, rewards, split, opts, seed=0, device="cuda", init=None):
     return best, last, info
 
 
-def load_maps(data_dir, stage):
-    """lib/data.py:87-124: every image directory's stage{N}_{name}_features.npy, in sorted order."""
+def load_maps(data_dir, stage, names=V5_NAMES):
+    """lib/data.py:87-124: every image directory's stage{N}_{name}_features.npy, in sorted order.  names: the
+    stage -> name table (a list or a dict): YOLOv5's, or SSDLite's (edgeml_amd.tapnet.ssd_names())."""
     images = sorted(f for f in os.listdir(data_dir) if not os.path.isfile(os.path.join(data_dir, f)))
-    return [np.load(os.path.join(data_dir, im, f"stage{stage}_{V5_NAMES[stage]}_features.npy"), allow_pickle=False)
+    return [np.load(os.path.join(data_dir, im, f"stage{stage}_{names[stage]}_features.npy"), allow_pickle=False)
             for im in images]
 
 
@@ -536,10 +541,17 @@ def save_state(path, spec, state, index):
 
 def check_args(opts):
     """Refuse what this CLI does not build, naming what does."""
-    if opts.stage == 24:
+    if getattr(opts, "weak", "yolov5") == "ssd":
+        from . import tapnet
+        try:
+            tapnet.stage_info(opts.stage)
+        except ValueError as e:
+            raise SystemExit(f"--weak ssd --stage {opts.stage}: not in SSDLite's stage table (edgeml_amd.tapnet."
+                             f"stage_table: 1-16 mobilenet_v3_large.features, 17-20 backbone.extra): {e}") from None
+    elif opts.stage == 24:
         raise SystemExit("edgeml_amd.convnet trains on the hidden-layer feature maps of stages 0-23; --stage 24 (the "
                          "output features) is python -m edgeml_amd.estimator")
-    if not 0 <= opts.stage < 24:
+    elif not 0 <= opts.stage < 24:
         raise SystemExit(f"--stage {opts.stage}: the YOLOv5 stages are 0-23 (and 24, the output features)")
     if opts.model != "CNN":
         raise SystemExit("Only fully convolutional NN can take feature maps from hidden layers as inputs: "
@@ -547,6 +559,8 @@ def check_args(opts):
     if not opts.channels:
         raise SystemExit("--channels: give the output channels of every conv layer (e.g. --channels 64 32); a net "
                          "without conv layers on the stage-24 features is python -m edgeml_amd.estimator")
+    if opts.epochs < 1:
+        raise SystemExit("--epochs: at least one epoch")
     if opts.resize < 0:
         raise SystemExit("--resize: 0 (keep the maps' shapes) or the side S of the pooled maps")
     n = len(opts.channels)
@@ -561,10 +575,14 @@ def check_args(opts):
 
 def main(opts):
     kernels, pools = check_args(opts)
-    maps = load_maps(opts.data_dir, opts.stage)
+    if opts.weak == "ssd":
+        from . import tapnet
+        maps = load_maps(opts.data_dir, opts.stage, tapnet.ssd_names())
+    else:
+        maps = load_maps(opts.data_dir, opts.stage)
     reward, split = estimator.load_reward_split(opts, len(maps))
     cnn = ConvOpt(channels=list(opts.channels), kernels=kernels, pools=pools, hidden=list(opts.hidden),
-                  resize=opts.resize > 0, weight=opts.weight and opts.normalize)
+                  resize=opts.resize > 0, weight=opts.weight and opts.normalize, max_epoch=opts.epochs)
     try:
         feats = pool_maps(maps, opts.resize) if cnn.resize else maps
         if not cnn.resize:
@@ -594,6 +612,9 @@ def getargs(argv=None):
     a.add_argument("--pools", type=int, nargs="*", default=None, help="1: MaxPool2d(2, 2) after the layer; default 1 1 0 ...")
     a.add_argument("--hidden", type=int, nargs="*", default=[16, 16, 16, 16], help="hidden linear widths")
     a.add_argument("--seed", type=int, default=0)
+    a.add_argument("--epochs", type=int, default=100, help="training epochs (the reference's max_epoch, 100)")
+    a.add_argument("--weak", choices=("yolov5", "ssd"), default="yolov5",
+                   help="whose hidden-layer maps data_dir holds: YOLOv5's, or SSDLite's (python -m edgeml_amd.maps)")
     return a.parse_args(argv)
 
 

@@ -136,6 +136,61 @@ inline bool mbconv_fits(int K, int stride, int Cin, int Cout, int Cexp) {
            mbconv_lds(K, stride, Cin, Cexp) <= (size_t)MBW_LDS_MAX;
 }
 
+// The eval-mode conv-stack net (edgeml_amd.convnet's EdgeDetectionNet with resize on) that one workgroup of
+// csrc/tapnet.hip runs per image.  Its activation planes -- the pooled input map, every conv output, every
+// pooled map (pixels x (channels + 1) floats: an odd pitch) and every hidden linear vector -- alternate between
+// two LDS regions, each as large as the largest plane it holds.
+constexpr int TAPNET_MAXL = 8;                 // conv layers, and linear layers, at most
+constexpr int TAPNET_LDS_MAX = 160 * 1024;     // the LDS of a CU
+struct TapnetShape {
+    int S, cin, nconv, nlin;
+    int cout[TAPNET_MAXL], k[TAPNET_MAXL], pool[TAPNET_MAXL];
+    int dims[TAPNET_MAXL + 1];  // linear widths: dims[0] the flattened conv output, dims[nlin] = 1
+};
+constexpr const char* TAPNET_DOMAIN =
+    "tapnet: S in 1..64, 1..8 conv layers (channel counts multiples of 4, odd kernels, a 2x2 pool only on a map of "
+    "at least 2x2), 1..8 linear layers from the flattened conv output down to 1, and the two LDS regions of the "
+    "activation planes within 160 KiB";
+// Floats of the two regions (plane p lives in region p & 1), or false when the shape is not a net at all.
+inline bool tapnet_regions(const TapnetShape& t, int64_t size[2]) {
+    size[0] = size[1] = 0;
+    if (t.S < 1 || t.S > 64 || t.nconv < 1 || t.nconv > TAPNET_MAXL || t.nlin < 1 || t.nlin > TAPNET_MAXL ||
+        t.cin < 4 || t.cin % 4 != 0 || t.cin > (1 << 16))
+        return false;
+    int r = 0, h = t.S, w = t.S, c = t.cin;
+    auto put = [&](int64_t n) {
+        if (n > size[r]) size[r] = n;
+        r ^= 1;
+    };
+    put((int64_t)h * w * (c + 1));
+    for (int i = 0; i < t.nconv; ++i) {
+        if (t.cout[i] < 4 || t.cout[i] % 4 != 0 || t.cout[i] > (1 << 16) || t.k[i] < 1 || t.k[i] % 2 == 0 || t.k[i] > 63)
+            return false;
+        c = t.cout[i];
+        put((int64_t)h * w * (c + 1));
+        if (t.pool[i]) {
+            if (h < 2 || w < 2) return false;
+            h /= 2;
+            w /= 2;
+            put((int64_t)h * w * (c + 1));
+        }
+    }
+    if (t.dims[0] != c * h * w || t.dims[t.nlin] != 1) return false;
+    for (int l = 1; l < t.nlin; ++l) {
+        if (t.dims[l] < 1 || t.dims[l] > (1 << 16)) return false;
+        put(t.dims[l]);
+    }
+    return true;
+}
+inline int64_t tapnet_lds(const TapnetShape& t) {
+    int64_t size[2];
+    return tapnet_regions(t, size) ? 4 * (size[0] + size[1]) : -1;
+}
+inline bool tapnet_fits(const TapnetShape& t) {
+    const int64_t n = tapnet_lds(t);
+    return n >= 0 && n <= TAPNET_LDS_MAX;
+}
+
 
 struct PoolParams {
     const float* x;

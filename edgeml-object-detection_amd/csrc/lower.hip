@@ -350,6 +350,14 @@ struct Plan {
     uint64_t last_use = 0;
     int input = -1, out_box = -1, out_score = -1, out_label = -1, out_count = -1;
     int dets = 0;
+    // SSDLite: where each backbone stage's output lives, per batch chain (edgedet_ssdlite_taps).  Not part of
+    // the records, the buffers or the workspace.
+    struct Tap {
+        int stage, chain, buf;
+        const char* token;
+        int64_t image0, images;
+    };
+    std::vector<Tap> taps;
 
     int buf(std::vector<int64_t> shape, int esize, const std::string& name) {
         Buf b;
@@ -842,6 +850,10 @@ class SSDLite {
             return conv(d.y, pf.pp, b.cout, 1, 1, A_NONE, res, scale);
         };
 
+        // the stage table: stage N = the output of mobilenet_v3_large.features[N], 17-20 the extra blocks
+        auto tap = [&](int stage, const char* token, const Cur& at) {
+            if (!pack_only) P.taps.push_back({stage, c, at.x.idx, token, img0, B});
+        };
         int first = 0;
         if (stem_fuse) {
             ConvW w0 = cbn("backbone.features.0.0", 16, 3, 3, false, 4);
@@ -865,21 +877,29 @@ class SSDLite {
             P.add(o);
             cur = Cur{P.ref(y), ys};
             first = 1;
+            tap(1, "IR", cur);  // the stem conv's own output (stage 0) never reaches memory
         } else {
             cur = conv(cur, "backbone.features.0.0", 16, 3, 2, A_HS, Ref(), Ref(), 4);
+            tap(0, "Conv", cur);
         }
-        for (int i = first; i < 12; ++i)
+        for (int i = first; i < 12; ++i) {
             cur = inverted_residual(cur, blocks_[(size_t)i], "backbone.features.0." + std::to_string(i + 1) + ".block");
+            tap(i + 1, "IR", cur);
+        }
         const Block& b12 = blocks_[12];
         cur = conv(cur, "backbone.features.0.13", b12.exp, 1, 1, b12.act);
         std::vector<Cur> feats = {cur};
         DwOut d = dw(cur, "backbone.features.1.0.1", b12.k, b12.stride, b12.act, true);
         Ref scale = se(d, "backbone.features.1.0.2");
         cur = conv(d.y, "backbone.features.1.0.3", b12.cout, 1, 1, A_NONE, Ref(), scale);
-        for (int i : {13, 14})
+        tap(13, "IR", cur);
+        for (int i : {13, 14}) {
             cur = inverted_residual(cur, blocks_[(size_t)i], "backbone.features.1." + std::to_string(i - 12) + ".block");
+            tap(i + 1, "IR", cur);
+        }
         const int c4 = blocks_[14].cout;
         cur = conv(cur, "backbone.features.1.3", 6 * c4, 1, 1, A_HS);
+        tap(16, "Conv", cur);
         feats.push_back(cur);
         const int outs[4] = {512, 256, 256, 128};
         for (int e = 0; e < 4; ++e) {
@@ -887,6 +907,7 @@ class SSDLite {
             cur = conv(cur, p + ".0", outs[e] / 2, 1, 1, A_R6);
             cur = dw(cur, p + ".1", 3, 2, A_R6, false).y;
             cur = conv(cur, p + ".2", outs[e], 1, 1, A_R6);
+            tap(17 + e, "Extra", cur);
             feats.push_back(cur);
         }
         std::vector<std::pair<int, int>> grids;
@@ -1991,6 +2012,43 @@ extern "C" int64_t edgedet_model_buffers(int32_t kind, int32_t num_classes, int3
                 for (int j = 0; j < r.ndim; ++j) r.shape[j] = b.shape[(size_t)j];
             }
         }
+        return n;
+    })
+}
+
+extern "C" int64_t edgedet_ssdlite_taps(int32_t num_classes, int32_t reduced_tail, int32_t B, int32_t H, int32_t W,
+                                        int32_t input_u8, int32_t stage, edgedet_tap* out, int64_t cap) {
+    Config c;
+    if (config_of(EDGEDET_MODEL_SSDLITE, num_classes, reduced_tail, &c) || shape_ok(B, H, W)) return -1;
+    EDGEDET_REQUIRE(stage >= -1 && stage <= 20,
+                    "ssdlite_taps: the stage table is 0-16 (mobilenet_v3_large.features) and 17-20 (backbone.extra)");
+    EDGEDET_TRY({
+        std::lock_guard<std::mutex> g(g_mu);
+        Plan* p = plan_for(engine(c), B, H, W, input_u8 != 0);
+        EDGEDET_REQUIRE(stage != 0 || !p->opt.stem_fuse,
+                        "ssdlite_taps: stage 0 (the stem conv) has no buffer under the fused stem; lower with "
+                        "EDGEDET_SSD_STEM_FUSE=0 to give it one");
+        std::vector<Plan::Tap> sel;
+        for (int s = stage < 0 ? 0 : stage; s <= (stage < 0 ? 20 : stage); ++s)
+            for (auto& t : p->taps)
+                if (t.stage == s) sel.push_back(t);
+        const int64_t n = (int64_t)sel.size();
+        if (out && cap >= n)
+            for (int64_t k = 0; k < n; ++k) {
+                const Plan::Tap& t = sel[(size_t)k];
+                const Buf& b = p->bufs[(size_t)t.buf];
+                edgedet_tap& r = out[k];
+                std::memset(&r, 0, sizeof(r));
+                r.stage = t.stage;
+                r.chain = t.chain;
+                std::strncpy(r.token, t.token, sizeof(r.token) - 1);
+                std::strncpy(r.buffer, b.name.c_str(), sizeof(r.buffer) - 1);
+                r.image0 = t.image0;
+                r.images = t.images;
+                r.H = b.shape[1];
+                r.W = b.shape[2];
+                r.C = b.shape[3];
+            }
         return n;
     })
 }

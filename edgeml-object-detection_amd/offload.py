@@ -5,9 +5,17 @@ threshold (the policy test.py:30-42 simulates on saved files, run for real in on
     python -m edgeml_amd.offload img_dir save_dir --estimator WTS (--ratio R --estimates EST_DIR | --threshold T)
            [--fold 1] [--k 25] [--dataset coco|voc] [--weak ssd] [--strong faster_rcnn]
            [--weak-path P] [--strong-path P] [--weak-dir DIR] [--weak-batch N] [--strong-batch N]
-           [--decode gpu|host]
+           [--decode gpu|host] [--stage N --resize S [--pools P ...] [--fused]]
 
-WTS is a trained estimator: wts<fold>.pickle as `edgeml_amd.estimator --model LR|EN|BR --model-dir` or
+With --stage N, WTS is a conv-stack estimator of `edgeml_amd.convnet --weak ssd --stage N --resize S --model-dir`
+(conv_stacks.* tensors): the decision is taken from the weak detector's own stage-N map.  The hook pools each batch
+chain's tapped buffer (edgeml_amd.tapnet.stage_table) to S x S with one edgedet_roi_align call -- convnet.pool_maps'
+launcher and arguments, so the pooled values are the training route's bits -- and the layered eval forward
+(convnet.Trainer.forward(train=False)) or, with --fused, one fused launch (csrc/tapnet.hip; a net outside its fit
+rule is refused) writes the estimates and flags.  The layered forward is the default: in the weak stage the fused
+kernel measured no faster.  A --resize 0 file runs the layered forward on the tapped map itself.
+
+Otherwise WTS is a trained estimator on the stage-24 output features: wts<fold>.pickle as `edgeml_amd.estimator --model LR|EN|BR --model-dir` or
 `edgeml_amd.svr --model LSVR --model-dir` writes it (plain numpy mean, scale, coef, intercept), wts<fold>.pth
 as `--model CNN --model-dir` writes it (the MLP's tensors under EdgeDetectionNet's state-dict names; the
 layer widths are read from the weight shapes), or the wts<fold>.pickle of `edgeml_amd.svr --model SVR` (the
@@ -56,7 +64,9 @@ class Estimator:
     """A trained reward estimator on `width` stage-24 features: kind "linear" (mean, scale, coef
     float64 [width], intercept), "mlp" (dims, state float32 in estimator.MlpSpec's layout), or "svr" /
     "knr" (model: the kpredict.KernelModel that predicts from the file's stored rows), or "gbr" (model: the
-    gbr.GBRModel that walks the file's trees), or "rfr" (model: the rfr.RFRModel that walks the file's forest)."""
+    gbr.GBRModel that walks the file's trees), or "rfr" (model: the rfr.RFRModel that walks the file's forest).
+    Kind "convnet" reads no stage-24 features: net (a tapnet.TapNet) predicts from the weak detector's stage-`stage`
+    map (map_shape = its C, H, W) pooled to resize x resize (0: the map itself, a --resize 0 net)."""
 
     def __init__(self, kind, width, **data):
         self.kind, self.width = kind, int(width)
@@ -114,8 +124,15 @@ def _check_width(path, what, have, width, consistent=True):
                          f"(num_class + 5 k: check --k and --dataset)")
 
 
-def load_estimator(path, width, support=False):
-    """The estimator of a wts<fold>.pickle / wts<fold>.pth file (an LSVR file of edgeml_amd.svr is a linear
+def load_estimator(path, width, support=False, stage=None, resize=None, pools=None, num_classes=91, reduced_tail=True,
+                   fused=None):
+    """With stage=N: the conv-stack file of edgeml_amd.convnet as kind "convnet" (net: a tapnet.TapNet whose
+    ConvSpec is rebuilt from the tensor shapes, for the SSDLite stage-N map of (num_classes, reduced_tail) pooled
+    to resize x resize; pools: the net's pools when not the convnet CLI's default).  ValueError when the first conv
+    layer's Cin is not the stage's channel count, when the first linear width is not the pooled geometry's, and
+    for a stage the table does not have.  Without stage, as before:
+
+    The estimator of a wts<fold>.pickle / wts<fold>.pth file (an LSVR file of edgeml_amd.svr is a linear
     model).  A KNR file that holds its training rows ('train', 'target') loads as kind "knr"; with
     support=True (what the cascade passes) an SVR file loads as kind "svr", otherwise it is refused as before;
     a GBR file of edgeml_amd.gbr loads as kind "gbr", an RFR file of edgeml_amd.rfr as kind "rfr".
@@ -126,6 +143,18 @@ def load_estimator(path, width, support=False):
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
         named = {k: v.numpy() for k, v in named.items() if torch.is_tensor(v)}
+        if stage is not None:
+            from . import tapnet
+            if not any(k.startswith("conv_stacks.") for k in named):
+                raise ValueError(f"{path}: --stage {stage} takes a conv-stack estimator of edgeml_amd.convnet "
+                                 "(conv_stacks.* tensors); this file has none")
+            token, C, H, W = tapnet.stage_info(stage, num_classes, reduced_tail)
+            spec = tapnet.spec_from_named(path, named, C, resize, pools)
+            if fused and not tapnet.TapNet(spec, spec.pack(named)).fits:
+                raise ValueError(f"{path}: --fused: the net is outside the fused kernel's fit rule "
+                                 "(edgedet_tapnet_fits); drop --fused for the layered forward")
+            return Estimator("convnet", width, net=tapnet.TapNet(spec, spec.pack(named), fused=fused), stage=int(stage),
+                             resize=int(resize or 0), map_shape=(C, H, W))
         if any(k.startswith("conv_stacks.") for k in named):
             raise ValueError(f"{path}: a conv-stack estimator of edgeml_amd.convnet (conv_stacks.* tensors): it reads the "
                              "weak detector's hidden-layer feature maps, which the cascade does not have; use an "
@@ -149,6 +178,9 @@ def load_estimator(path, width, support=False):
         m = pickle.load(f)
     if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
         raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
+    if stage is not None:
+        raise ValueError(f"{path}: --stage {stage} takes a conv-stack wts<fold>.pth of edgeml_amd.convnet; this "
+                         "estimator reads the stage-24 output features (drop --stage and --resize)")
     if m.get("model") == "SVR" and not support:
         raise ValueError(f"{path}: an SVR file holds support vectors, and the cascade does not predict from them "
                          f"yet; train --model LSVR, LR, EN, BR or CNN")
@@ -162,6 +194,23 @@ def load_estimator(path, width, support=False):
     mean, scale, coef = (np.ascontiguousarray(np.asarray(m[k], np.float64).reshape(-1)) for k in ("mean", "scale", "coef"))
     _check_width(path, "model", len(coef), width, len(mean) == len(scale) == len(coef))
     return Estimator("linear", width, mean=mean, scale=scale, coef=coef, intercept=float(m["intercept"]))
+
+
+def _has_conv_stacks(path):
+    named = torch.load(path, map_location="cpu", weights_only=True)
+    return any(str(k).startswith("conv_stacks.") for k in named)
+
+
+def _weak_tail(opts):
+    """The tail of the weak SSDLite the detect CLI would load (detect.load_weak_models): the COCO-pretrained
+    reduced tail without --weak-path, else what the file's tensors say."""
+    if not opts.weak_path:
+        return True
+    sd = torch.load(opts.weak_path, map_location="cpu", weights_only=True)
+    if isinstance(sd, dict) and "model" in sd and not torch.is_tensor(sd["model"]):
+        sd = sd["model"]
+    w = sd.get("backbone.features.1.3.0.weight")
+    return True if w is None else tuple(w.shape)[1] == 80
 
 
 def ratio_threshold(train_est, ratio):
@@ -267,6 +316,53 @@ class Chain:
     def __init__(self, estimator, threshold, num_class, k, dataset):
         self.est, self.threshold, self.num_class, self.k, self.dataset = estimator, float(threshold), num_class, k, dataset
 
+    def map_buffers(self, plan, sl):
+        """The convnet estimator's slot state: the plan's taps of its stage, the whole-image RoIs of every chain,
+        the pooled maps and, for the layered path, one Trainer (its activation buffers belong to this slot's
+        stream)."""
+        from . import tapnet
+        e, B = self.est, plan.B
+        buf = sl.get("offload")
+        fused = e.net.use_fused()
+        if buf is None or buf["key"] != (B, e.stage, e.resize, fused, id(e.net)):
+            dev = plan.device
+            model = plan.model
+            taps = tapnet.stage_table(model.num_classes, model.reduced_tail, B, plan.H, plan.W, plan.u8, e.stage)
+            C, H, W = taps[0].C, taps[0].H, taps[0].W
+            if (C, H, W) != tuple(e.map_shape):
+                raise ValueError(f"stage {e.stage}: the plan's map is {(C, H, W)}, the estimator was loaded for "
+                                 f"{tuple(e.map_shape)} (check --dataset and the weak model's tail)")
+            d = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+            p = lambda shape, dt: torch.zeros(shape, dtype=dt, pin_memory=True)  # noqa: E731
+            n = max(t.images for t in taps)
+            rois = np.zeros((n, 5), np.float32)  # lib/data.py load_feature: box [0, 0, w, h] of image i
+            rois[:, 0], rois[:, 3], rois[:, 4] = np.arange(n), W, H
+            S = e.resize
+            buf = sl["offload"] = {
+                "key": (B, e.stage, e.resize, fused, id(e.net)), "taps": [(t, plan.buffer(t.buffer).tensor()) for t in taps],
+                "rois": torch.from_numpy(rois).to(dev), "pooled": d((B, S, S, C), torch.float32) if S else None,
+                "trainer": None if fused else e.net.trainer(dev, B if S else n, H * W),
+                "est": d((B,), torch.float64), "flag": d((B,), torch.uint8), "count": d((1,), torch.int32),
+                "index": d((B,), torch.int32),
+                "h_est": p((B,), torch.float64), "h_flag": p((B,), torch.uint8), "h_count": p((1,), torch.int32),
+                "h_index": p((B,), torch.int32)}
+        return buf
+
+    def decide_from_maps(self, plan, b, stream):
+        """Pool each chain's tapped buffer (one edgedet_roi_align call per chain), then the estimates and flags
+        of the batch."""
+        e, S = self.est, self.est.resize
+        for t, x in b["taps"]:
+            if S:
+                out = b["pooled"][t.image0:t.image0 + t.images]
+                ops.check(ops.lib().edgedet_roi_align(ops._ptr(x), t.images, t.H, t.W, t.C, ops._ptr(b["rois"]),
+                                                      t.images, 1.0, S, S, 0, ops._ptr(out), ops.stream_handle(stream)))
+            else:  # a --resize 0 net reads the map itself: the layered forward, chain by chain
+                sl = slice(t.image0, t.image0 + t.images)
+                e.net.infer(x, self.threshold, b["est"][sl], b["flag"][sl], stream, b["trainer"])
+        if S:
+            e.net.infer(b["pooled"], self.threshold, b["est"], b["flag"], stream, b["trainer"])
+
     def buffers(self, plan, sl):
         B, K = (int(v) for v in plan.out_score.shape)
         D = self.num_class + 5 * self.k
@@ -289,11 +385,15 @@ class Chain:
     def __call__(self, plan, sl, stream, tag):
         if not plan.u8:
             raise ValueError("the cascade packs the decoded uint8 images: the weak batches must be uint8")
-        b = self.buffers(plan, sl)
-        format_rows(plan.out_count.tensor(), plan.out_box.tensor(), plan.out_score.tensor(), plan.out_label.tensor(),
-                    plan.H, plan.W, self.dataset, b["rows"], b["nrow"], stream)
-        row_features(b["rows"], b["nrow"], self.num_class, self.k, b["feat"], stream)
-        self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"], b["kws"]), stream)
+        if self.est.kind == "convnet":
+            b = self.map_buffers(plan, sl)
+            self.decide_from_maps(plan, b, stream)
+        else:
+            b = self.buffers(plan, sl)
+            format_rows(plan.out_count.tensor(), plan.out_box.tensor(), plan.out_score.tensor(),
+                        plan.out_label.tensor(), plan.H, plan.W, self.dataset, b["rows"], b["nrow"], stream)
+            row_features(b["rows"], b["nrow"], self.num_class, self.k, b["feat"], stream)
+            self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"], b["kws"]), stream)
         images = plan.input.tensor()
         packed = torch.empty_like(images)  # this batch's own: it outlives the slot's next use
         pack(b["flag"], images, packed, b["count"], b["index"], stream)
@@ -321,7 +421,7 @@ def run(img_dir, estimator, threshold, k=25, dataset="coco", weak="ssd", strong=
     det_classes = 91 if dataset == "coco" else 21   # classes of the detectors (detect.main)
     if not isinstance(estimator, Estimator):
         estimator = load_estimator(estimator, num_class + 5 * k, support=True)
-    if estimator.width != num_class + 5 * k:
+    if estimator.kind != "convnet" and estimator.width != num_class + 5 * k:
         raise ValueError(f"the estimator takes {estimator.width} features, the cascade makes {num_class + 5 * k}")
     torch.cuda.set_device(device)
     data = detect.ObjectDetectionDataset(img_dir)
@@ -404,8 +504,20 @@ def main(opts):
         raise SystemExit("edgeml_amd.offload runs in one process on one GPU: sharding the cascade over several "
                          "GPUs is not built (run it without torchrun)")
     num_class = 20 if opts.dataset == "voc" else 80
+    if (opts.stage is None) != (opts.resize is None):
+        raise SystemExit("edgeml_amd.offload: --stage N and --resize S go together (a conv-stack estimator of "
+                         "edgeml_amd.convnet on the weak detector's stage-N map pooled to S x S; --resize 0 for a "
+                         "net trained with --resize 0)")
+    if opts.stage is not None and opts.weak != "ssd":
+        raise SystemExit("edgeml_amd.offload: --stage reads SSDLite's stage table; --weak ssd is the only producer")
     try:
-        estimator = load_estimator(opts.estimator, num_class + 5 * opts.k, support=True)  # before any image is read
+        if opts.stage is None and str(opts.estimator).endswith(".pth") and _has_conv_stacks(opts.estimator):
+            raise ValueError(f"{opts.estimator}: a conv-stack estimator of edgeml_amd.convnet: give --stage N (the "
+                             "SSDLite stage it was trained on) and --resize S (its --resize)")
+        estimator = load_estimator(opts.estimator, num_class + 5 * opts.k, support=True, stage=opts.stage,
+                                   resize=opts.resize, pools=opts.pools,
+                                   num_classes=91 if opts.dataset == "coco" else 21,
+                                   reduced_tail=_weak_tail(opts), fused=True if opts.fused else None)
     except ValueError as e:
         raise SystemExit(f"edgeml_amd.offload: {e}") from None
     threshold = resolve_threshold(opts)
@@ -455,6 +567,12 @@ def getargs(argv=None):
     a.add_argument("--weak-batch", type=int, default=0, help="Images per weak engine call (0 = model default).")
     a.add_argument("--strong-batch", type=int, default=0, help="Images per strong engine call (0 = model default).")
     a.add_argument("--decode", choices=("gpu", "host"), default="gpu")
+    a.add_argument("--stage", type=int, default=None, help="Decide from the weak detector's stage-N map (SSDLite's "
+                   "stage table) with a conv-stack estimator of edgeml_amd.convnet; needs --resize.")
+    a.add_argument("--resize", type=int, default=None, help="The side S the maps are pooled to (the net's --resize).")
+    a.add_argument("--pools", type=int, nargs="*", default=None, help="The net's --pools when not the default 1 1 0 ...")
+    a.add_argument("--fused", action="store_true", help="Run the conv-stack estimator as one fused launch "
+                   "(csrc/tapnet.hip) instead of the layered eval forward.")
     opts = a.parse_args(argv)
     if (opts.threshold is None) == (opts.ratio is None):
         a.error("give either --threshold T or --ratio R with --estimates EST_DIR")

@@ -78,7 +78,10 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_frcnn_workspace_size", "edgedet_frcnn_forward", "edgedet_plan_check", "edgedet_release_lanes",
            "edgedet_lane_sets", "edgedet_nms_workspace_size", "edgedet_nms_ws", "edgedet_batched_nms_ws",
            "edgedet_topk_segments", "edgedet_box_decode", "edgedet_jpeg_packet", "edgedet_jpeg_batch_packets", "edgedet_jpeg_plane_bytes", "edgedet_image_dims",
-           "edgedet_jpeg_decode_batch", "edgedet_jpeg_reconstruct_host", "edgedet_model_buffers", "edgedet_model_op_names", "edgedet_model_release")
+           "edgedet_jpeg_decode_batch", "edgedet_jpeg_reconstruct_host", "edgedet_model_buffers", "edgedet_model_op_names", "edgedet_model_release",
+           "edgedet_ssdlite_taps", "edgedet_tapnet_fits", "edgedet_tapnet_lds", "edgedet_tapnet_infer",
+           "edgedet_tapnet_finish")
+TAPNET_NOFIT = -4  # include/edgedet.h EDGEDET_TAPNET_NOFIT
 
 
 class EdgeDetUnavailable(RuntimeError):
@@ -261,6 +264,18 @@ def lib():
     L.edgedet_model_op_names.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_char_p, _i64]
     L.edgedet_model_op_names.restype = _i64
     L.edgedet_model_release.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32]
+    # the stage table and the fused conv-stack inference (csrc/lower.hip, csrc/tapnet.hip)
+    L.edgedet_ssdlite_taps.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64]
+    L.edgedet_ssdlite_taps.restype = _i64
+    _net = [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]  # S, cin, nconv, channels, kernels, pools, nlin, dims
+    L.edgedet_tapnet_fits.argtypes = _net
+    L.edgedet_tapnet_fits.restype = ctypes.c_int
+    L.edgedet_tapnet_lds.argtypes = _net
+    L.edgedet_tapnet_lds.restype = _i64
+    L.edgedet_tapnet_infer.argtypes = [_vp, _i64] + _net + [_vp, _i64, _dbl, _vp, _vp, _vp]
+    L.edgedet_tapnet_infer.restype = ctypes.c_int
+    L.edgedet_tapnet_finish.argtypes = [_vp, _i64, _dbl, _vp, _vp, _vp]
+    L.edgedet_tapnet_finish.restype = ctypes.c_int
     L.edgedet_ssdlite_workspace_size.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32]
     L.edgedet_ssdlite_workspace_size.restype = _i64
     L.edgedet_ssdlite_forward.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]

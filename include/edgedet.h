@@ -801,6 +801,52 @@ int edgedet_cnn_loss(const float* pred, const float* y, int64_t n, int32_t weigh
 int edgedet_cnn_adam(float* param, const float* grad, float* m, float* v, int64_t n, float step_size, float bc2_sqrt,
                      float weight_decay, void* stream);
 
+/* ------------------------- the cascade's decision from a hidden-layer map (csrc/tapnet.hip, csrc/lower.hip) */
+/*
+ * edgedet_ssdlite_taps: the stage table of the SSDLite plan of (num_classes, reduced_tail, B, H, W, input_u8).
+ *   Stage N is the output of torchvision's mobilenet_v3_large.features[N] (1-15: the InvertedResidual blocks,
+ *   token "IR"; 16: the last 1x1 conv, "Conv"; 0: the stem conv, "Conv") and stages 17-20 are backbone.extra.0-3
+ *   ("Extra").  Every batch chain of the plan has a tap per stage: the workspace buffer [images][H][W][C] that
+ *   holds the stage's output for the chain's images [image0, image0 + images) of the batch.  stage >= 0: the
+ *   taps of that stage, one per chain in chain order; stage = -1: every tap, by stage then chain.  Returns the
+ *   count and fills out[] when cap is large enough; -1 (edgedet_last_error) for a stage outside the table, and
+ *   for stage 0 under the fused stem (EDGEDET_SSD_STEM_FUSE=1, the default), where the stem conv's output never
+ *   reaches memory.
+ */
+typedef struct edgedet_tap {
+    int32_t stage;
+    int32_t chain;
+    char token[8];    /* the file-name token: stage{N}_{token}_features.npy */
+    char buffer[96];  /* the workspace buffer's name (edgedet_model_buffers) */
+    int64_t image0, images, C, H, W;
+} edgedet_tap;
+int64_t edgedet_ssdlite_taps(int32_t num_classes, int32_t reduced_tail, int32_t B, int32_t H, int32_t W,
+                             int32_t input_u8, int32_t stage, edgedet_tap* out, int64_t cap);
+/*
+ * The eval-mode forward of edgeml_amd.convnet's conv-stack net (resize on) as one launch, one workgroup per
+ * image: x [B][S][S][cin] the pooled maps, `channels` / `kernels` / `pools` [nconv] the conv layers (output
+ * channels, odd kernel size, 1 = MaxPool 2x2 after it), dims [nlin + 1] the linear widths (dims[0] = the
+ * flattened last map, dims[nlin] = 1), state [ns] the net's state vector in ConvSpec's layout.  Writes
+ * est[b] = (double) the float32 estimate and flag[b] = est[b] > threshold (strict, as edgedet_offload_flag).
+ * Conv layers are implicit GEMMs on v_mfma_f32_16x16x4_f32 with K = (kh, kw, ci) ascending in one chain per
+ * output; BatchNorm is cnn_act_fwd's mode 2; linear sums are edgedet_cnn_linear_fwd's.  No atomics: an
+ * image's estimate does not depend on the batch it runs in.
+ * edgedet_tapnet_fits: 1 when the net is inside the kernel's domain (kernels.hpp tapnet_fits: the activation
+ *   planes' two LDS regions within 160 KiB, channel counts multiples of 4, odd kernels), else 0;
+ *   edgedet_tapnet_lds: the bytes of those regions (-1: not a net).  edgedet_tapnet_infer returns
+ *   EDGEDET_TAPNET_NOFIT for a net outside the domain, before it looks at any pointer.
+ * edgedet_tapnet_finish: est = (double) est32, flag = est > threshold: the tail of the layered eval forward.
+ */
+#define EDGEDET_TAPNET_NOFIT (-4)
+int edgedet_tapnet_fits(int32_t S, int32_t cin, int32_t nconv, const int32_t* channels, const int32_t* kernels,
+                        const int32_t* pools, int32_t nlin, const int32_t* dims);
+int64_t edgedet_tapnet_lds(int32_t S, int32_t cin, int32_t nconv, const int32_t* channels, const int32_t* kernels,
+                           const int32_t* pools, int32_t nlin, const int32_t* dims);
+int edgedet_tapnet_infer(const float* x, int64_t B, int32_t S, int32_t cin, int32_t nconv, const int32_t* channels,
+                         const int32_t* kernels, const int32_t* pools, int32_t nlin, const int32_t* dims,
+                         const float* state, int64_t ns, double threshold, double* est, uint8_t* flag, void* stream);
+int edgedet_tapnet_finish(const float* est32, int64_t B, double threshold, double* est, uint8_t* flag, void* stream);
+
 /* --------------------------------------------------------------------------------- misc */
 const char* edgedet_last_error(void);
 /* Library/ABI version: (major << 16) | minor. */
