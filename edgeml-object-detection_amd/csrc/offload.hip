@@ -11,6 +11,10 @@
 //                           features), then flag = estimate > threshold (test.py:37);
 //   edgedet_offload_flag    that flag alone, for estimates another call wrote (csrc/kpredict.hip's SVR and
 //                           KNR predictions): the same kernel;
+//   offload_dcsb_kernel     the DCSB baseline's rule (baseline.py:129-141) on the padded rows: counts above the
+//                           model's confidence threshold and above 0.5, the minimum area, est = 0.0 / 1.0;
+//   offload_svm_kernel      the Adaptive Feeding baseline's decision value on the stage-24 features, in the
+//                           summation order of csrc/baseline.hip's svm_rows_dot, flag = value > 0;
 //   offload_pack_kernel     the flagged images of a uint8 batch copied to the front of a destination
 //                           batch in index order (flags read on the device), with their count and
 //                           source indices;
@@ -19,6 +23,7 @@
 //
 // Every float op of the formatter is individually rounded (the _rn intrinsics, and the build's
 // -ffp-contract=off), so its rows are numpy's bytes.  The caller owns every buffer.
+#include "fold_math.hpp"
 #include "kernels.hpp"
 
 namespace edgedet {
@@ -120,6 +125,78 @@ __global__ void offload_flag_kernel(const float* __restrict__ est32, double* __r
     flag[i] = e > threshold ? 1 : 0;
 }
 
+// The smaller of two float64 values, a NaN winning from either side (np.amin): whatever the order of the
+// reduction, the result is the same value.
+__device__ __forceinline__ double min_nan(double a, double b) { return (a < b || a != a) ? a : b; }
+
+// DCSB's decision (baseline.py:129-141) for one fitted model.  One wave per image, 64 of its rows per pass:
+// the two counts from ballots, the minimum area of the rows above conf_thresh per lane and then across the
+// wave.  xywh2xyxy and get_area in the reference's operation order, each op rounded on its own.
+__global__ void __launch_bounds__(64) offload_dcsb_kernel(const double* __restrict__ rows,
+                                                          const int32_t* __restrict__ nrow, int K, double conf_thresh,
+                                                          int num_thresh, double area_thresh,
+                                                          int32_t* __restrict__ est_num, int32_t* __restrict__ det_num,
+                                                          double* __restrict__ min_area, double* __restrict__ est,
+                                                          uint8_t* __restrict__ flag) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int n = nrow[b];
+    n = n < 0 ? 0 : (n > K ? K : n);
+    const double* R = rows + (int64_t)b * K * 6;
+    int ne = 0, nd = 0;
+    double amin = __builtin_inf();  // of this lane's rows above conf_thresh
+    for (int k0 = 0; k0 < n; k0 += 64) {
+        const int k = k0 + lane;
+        bool over = false, det = false;
+        if (k < n) {
+            const double* r = R + (int64_t)k * 6;
+            const double conf = r[5];
+            over = conf > conf_thresh;
+            det = conf > 0.5;
+            if (over) {
+                const double x1 = r[1] - r[3] / 2, y1 = r[2] - r[4] / 2;
+                const double x2 = r[1] + r[3] / 2, y2 = r[2] + r[4] / 2;
+                amin = min_nan((x2 - x1) * (y2 - y1), amin);
+            }
+        }
+        ne += __popcll(__ballot(over));
+        nd += __popcll(__ballot(det));
+    }
+    for (int s = 32; s > 0; s >>= 1) amin = min_nan(amin, __shfl_xor(amin, s, 64));
+    if (lane != 0) return;
+    if (ne == 0) amin = 0.0;  // filter_box: 0 for an image without a row above the threshold
+    const bool cls = ne != nd && (ne > num_thresh || amin < area_thresh);
+    if (est_num) est_num[b] = ne;
+    if (det_num) det_num[b] = nd;
+    if (min_area) min_area[b] = amin;
+    est[b] = cls ? 1.0 : 0.0;
+    flag[b] = cls ? 1 : 0;
+}
+
+// Adaptive Feeding's decision on unpadded features: svm_rows_dot (csrc/baseline.hip) on the row
+// (feat[b], 1, 0, ...) of baseline.pad_features without that row in memory.  Sixteen lanes per image, lane
+// `sub` adds its terms k = sub, sub + 16, ... < Dp in increasing k from 0.0, then lane16_sum: the same
+// operations on the same values in the same order, so the sum is svm_decision_kernel's bit for bit.
+__global__ void __launch_bounds__(OFFLOAD_NT) offload_svm_kernel(const double* __restrict__ feat, int B, int D,
+                                                                 const double* __restrict__ v, int Dp,
+                                                                 double* __restrict__ est,
+                                                                 uint8_t* __restrict__ flag) {
+    __shared__ double sv[FOLD_MAXD];
+    if ((int)threadIdx.x < Dp) sv[threadIdx.x] = v[threadIdx.x];
+    __syncthreads();
+    const int sub = threadIdx.x & 15;
+    const int64_t b = (int64_t)blockIdx.x * (OFFLOAD_NT / 16) + (threadIdx.x >> 4);
+    const bool ok = b < B;
+    const double* row = feat + (ok ? b : 0) * D;
+    double acc = 0.0;
+    if (ok)
+        for (int k = sub; k < Dp; k += 16) acc += (k < D ? row[k] : (k == D ? 1.0 : 0.0)) * sv[k];
+    acc = lane16_sum(acc);
+    if (ok && sub == 0) {
+        est[b] = acc;
+        flag[b] = acc > 0.0 ? 1 : 0;  // fit_af_folds' (dec > 0)
+    }
+}
+
 // n bytes by the calling workgroup's share of `parts` workgroups: 16-byte copies when both ends are
 // 16-byte aligned, the bytes past the last whole 16 (or all of them) one by one.
 __device__ __forceinline__ void copy_image(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t n,
@@ -217,6 +294,30 @@ extern "C" int edgedet_offload_flag(const double* est, int64_t B, double thresho
     // est32 null: the kernel only reads est
     hipLaunchKernelGGL(offload_flag_kernel, dim3((unsigned)cdiv(B, OFFLOAD_NT)), dim3(OFFLOAD_NT), 0,
                        (hipStream_t)stream, (const float*)nullptr, const_cast<double*>(est), B, threshold, flag);
+    EDGEDET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int edgedet_offload_dcsb(const double* rows, const int32_t* nrow, int64_t B, int64_t K, double conf_thresh,
+                                    int32_t num_thresh, double area_thresh, int32_t* est_num, int32_t* det_num,
+                                    double* min_area, double* est, uint8_t* flag, void* stream) {
+    EDGEDET_REQUIRE(rows && nrow && est && flag, "offload_dcsb: null pointer");
+    EDGEDET_REQUIRE(B >= 0 && B <= 65535 && K >= 1 && K < (1 << 24), "offload_dcsb: bad sizes");
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(offload_dcsb_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, rows, nrow, (int)K,
+                       conf_thresh, num_thresh, area_thresh, est_num, det_num, min_area, est, flag);
+    EDGEDET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int edgedet_offload_svm(const double* feat, int64_t B, int64_t D, const double* v, int64_t Dp, double* est,
+                                   uint8_t* flag, void* stream) {
+    EDGEDET_REQUIRE(feat && v && est && flag, "offload_svm: null pointer");
+    EDGEDET_REQUIRE(B >= 0 && B <= 65535 && fold_dims_ok(D) && Dp <= FOLD_MAXD && Dp == (D + 1 + 15) / 16 * 16,
+                    "offload_svm: Dp = D + 1 padded to a multiple of 16, <= 256");
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(offload_svm_kernel, dim3((unsigned)cdiv(B, (int64_t)(OFFLOAD_NT / 16))), dim3(OFFLOAD_NT), 0,
+                       (hipStream_t)stream, feat, (int)B, (int)D, v, (int)Dp, est, flag);
     EDGEDET_LAUNCH_CHECK();
     return 0;
 }

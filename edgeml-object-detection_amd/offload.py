@@ -6,6 +6,17 @@ threshold (the policy test.py:30-42 simulates on saved files, run for real in on
            [--fold 1] [--k 25] [--dataset coco|voc] [--weak ssd] [--strong faster_rcnn]
            [--weak-path P] [--strong-path P] [--weak-dir DIR] [--weak-batch N] [--strong-batch N]
            [--decode gpu|host] [--stage N --resize S [--pools P ...] [--fused]]
+    python -m edgeml_amd.offload img_dir save_dir --estimator WTS --baseline af|dcsb   [the other options as above]
+
+With --baseline, WTS is a saved comparison baseline, the wts<fold>.pickle of `edgeml_amd.baseline --model_dir`, and
+the cascade runs that policy instead of ours.  Both are classifiers: an image is offloaded where its class is 1, the
+threshold is 0.0, and --ratio, --estimates, --threshold, --stage, --resize, --pools and --fused are refused (a
+classifier has no ratio).  af (Adaptive Feeding) is the linear SVM {coef, intercept, classes [0, 1]} on the
+stage-24 features: rows -> features -> edgedet_offload_svm, whose decision value is edgedet_svm_decision's bit for
+bit on the padded features (baseline.pad_features' layout, the padding implied), flag = value > 0 as the fit's
+(dec > 0); `estimate` is the decision value.  dcsb is the tuple (conf_thresh, num_thresh, area_thresh):
+rows -> edgedet_offload_dcsb (baseline.py:129-141 on the padded rows, one wave per image; no features are made);
+`estimate` is 0.0 or 1.0.
 
 With --stage N, WTS is a conv-stack estimator of `edgeml_amd.convnet --weak ssd --stage N --resize S --model-dir`
 (conv_stacks.* tensors): the decision is taken from the weak detector's own stage-N map.  The hook pools each batch
@@ -58,6 +69,13 @@ from . import fmt, ops
 # ---------------------------------------------------------------------------------------- estimator file
 MODEL_KINDS = ("svr", "knr", "gbr", "rfr")  # an Estimator.model (kpredict.KernelModel, gbr.GBRModel, rfr.RFRModel)
 TREE_KINDS = ("gbr", "rfr")                 # ... of which these need no workspace
+CLASSIFIER_KINDS = ("af", "dcsb")           # the comparison baselines: a class, not a reward; the threshold is 0.0
+
+
+def _classifier_threshold(kind, threshold):
+    if float(threshold) != 0.0:
+        raise ValueError(f"the {kind} baseline is a classifier: it has no ratio and its threshold is 0.0, "
+                         f"not {float(threshold)!r}")
 
 
 class Estimator:
@@ -66,7 +84,11 @@ class Estimator:
     "knr" (model: the kpredict.KernelModel that predicts from the file's stored rows), or "gbr" (model: the
     gbr.GBRModel that walks the file's trees), or "rfr" (model: the rfr.RFRModel that walks the file's forest).
     Kind "convnet" reads no stage-24 features: net (a tapnet.TapNet) predicts from the weak detector's stage-`stage`
-    map (map_shape = its C, H, W) pooled to resize x resize (0: the map itself, a --resize 0 net)."""
+    map (map_shape = its C, H, W) pooled to resize x resize (0: the map itself, a --resize 0 net).
+    The two comparison baselines of edgeml_amd.baseline are classifiers (CLASSIFIER_KINDS; the threshold is 0.0):
+    kind "af" (v float64 [Dp]: the linear SVM's coef, its intercept at index width, zeros up to
+    Dp = (width + 1 + 15) // 16 * 16) and kind "dcsb" (conf_thresh, num_thresh, area_thresh; width 0: it reads
+    the detection rows, not the features)."""
 
     def __init__(self, kind, width, **data):
         self.kind, self.width = kind, int(width)
@@ -82,6 +104,10 @@ class Estimator:
             elif self.kind == "linear":
                 d = {"mean": t(self.mean), "scale": t(self.scale), "coef": t(self.coef),
                      "intercept": t(np.array([self.intercept], np.float64))}
+            elif self.kind == "af":
+                d = {"v": t(self.v)}
+            elif self.kind == "dcsb":
+                d = {}  # three scalars, passed by value
             else:
                 d = {"state": t(self.state)}
             self._dev = (torch.device(device), d)
@@ -92,11 +118,32 @@ class Estimator:
         the other kinds."""
         return self.model.workspace_bytes(B) if self.kind in MODEL_KINDS else 0
 
-    def decide(self, feat, threshold, est, flag, scratch, stream=None):
+    def decide(self, feat, threshold, est, flag, scratch=(), stream=None, rows=None, nrow=None):
         """edgedet_offload_decide on feat [B, width] float64 (device): est [B] float64 and flag [B] uint8
         are written on `stream`; scratch = (x32 [B, width], est32 [B]) float32 for an MLP.  An SVR or KNR
         model takes a third entry, its uint8 workspace (workspace_bytes(B)): its estimates are
-        kpredict.KernelModel's, then edgedet_offload_flag."""
+        kpredict.KernelModel's, then edgedet_offload_flag.  The classifiers take threshold 0.0 and no scratch:
+        "af" is edgedet_offload_svm on feat (est: the decision value, flag: value > 0), "dcsb" is
+        edgedet_offload_dcsb on rows [B, K, 6] and nrow [B] of format_rows (est: 0.0 / 1.0; feat is not read)."""
+        if self.kind in CLASSIFIER_KINDS:
+            _classifier_threshold(self.kind, threshold)
+            if self.kind == "dcsb":
+                ops._need_cuda(rows, nrow, est, flag)
+                if rows is None or nrow is None:
+                    raise ValueError("the dcsb baseline decides on the detection rows: give rows and nrow")
+                ops.check(ops.lib().edgedet_offload_dcsb(ops._ptr(rows), ops._ptr(nrow), int(rows.shape[0]),
+                                                         int(rows.shape[1]), float(self.conf_thresh), int(self.num_thresh),
+                                                         float(self.area_thresh), None, None, None, ops._ptr(est),
+                                                         ops._ptr(flag), ops.stream_handle(stream)))
+                return
+            ops._need_cuda(feat, est, flag)
+            if feat.dim() != 2 or int(feat.shape[1]) != self.width:
+                raise ValueError(f"the af baseline takes [B, {self.width}] features, got {tuple(feat.shape)}")
+            v = self.device_data(feat.device)["v"]
+            ops.check(ops.lib().edgedet_offload_svm(ops._ptr(feat), int(feat.shape[0]), self.width, ops._ptr(v),
+                                                    int(v.numel()), ops._ptr(est), ops._ptr(flag),
+                                                    ops.stream_handle(stream)))
+            return
         B = int(feat.shape[0])
         d = self.device_data(feat.device)
         if self.kind in MODEL_KINDS:
@@ -124,9 +171,54 @@ def _check_width(path, what, have, width, consistent=True):
                          f"(num_class + 5 k: check --k and --dataset)")
 
 
+def _is_af_file(m):
+    return isinstance(m, dict) and "coef" in m and "intercept" in m and "classes" in m and "mean" not in m
+
+
+def _is_dcsb_file(m):
+    return isinstance(m, tuple) and len(m) == 3
+
+
+def load_baseline(path, width, baseline):
+    """The wts<fold>.pickle of `edgeml_amd.baseline --model_dir` as a classifier Estimator.  baseline "af": the
+    dict {coef [width], intercept, classes [0, 1], ...} of the Adaptive Feeding SVM, as kind "af" with
+    baseline.pad_features' layout of the weights; baseline "dcsb": the tuple (conf_thresh float, num_thresh int,
+    area_thresh float), as kind "dcsb".  ValueError, naming what was expected, on any other file."""
+    import numbers
+    if baseline not in CLASSIFIER_KINDS:
+        raise ValueError(f"baseline {baseline!r}: one of {', '.join(CLASSIFIER_KINDS)}")
+    what = ("the Adaptive Feeding file of edgeml_amd.baseline --baseline af --model_dir "
+            "({coef, intercept, classes: [0, 1]})" if baseline == "af" else
+            "the DCSB file of edgeml_amd.baseline --baseline dcsb --model_dir "
+            "((conf_thresh float, num_thresh int, area_thresh float))")
+    m = None
+    if not str(path).endswith(".pth"):
+        with open(path, "rb") as f:
+            try:
+                m = pickle.load(f)
+            except (pickle.UnpicklingError, EOFError):
+                pass
+    if baseline == "af":
+        if not _is_af_file(m) or [int(c) for c in np.asarray(m["classes"]).reshape(-1)] != [0, 1]:
+            raise ValueError(f"{path}: --baseline af expects {what}")
+        coef = np.asarray(m["coef"], np.float64).reshape(-1)
+        _check_width(path, "Adaptive Feeding SVM", len(coef), width)
+        v = np.zeros((len(coef) + 1 + 15) // 16 * 16, np.float64)
+        v[:len(coef)], v[len(coef)] = coef, float(m["intercept"])
+        if len(v) > 256:
+            raise ValueError(f"{path}: {len(coef)} features + bias exceed the decision kernel's 256 columns")
+        return Estimator("af", width, v=v)
+    real = lambda x: isinstance(x, numbers.Real) and not isinstance(x, (bool, numbers.Integral))  # noqa: E731
+    if not _is_dcsb_file(m) or not real(m[0]) or not real(m[2]) or isinstance(m[1], bool) or \
+            not isinstance(m[1], numbers.Integral):
+        raise ValueError(f"{path}: --baseline dcsb expects {what}")
+    return Estimator("dcsb", 0, conf_thresh=float(m[0]), num_thresh=int(m[1]), area_thresh=float(m[2]))
+
+
 def load_estimator(path, width, support=False, stage=None, resize=None, pools=None, num_classes=91, reduced_tail=True,
-                   fused=None):
-    """With stage=N: the conv-stack file of edgeml_amd.convnet as kind "convnet" (net: a tapnet.TapNet whose
+                   fused=None, baseline=None):
+    """With baseline="af" | "dcsb": load_baseline (the saved comparison baselines of edgeml_amd.baseline; stage,
+    resize, pools and fused do not apply).  With stage=N: the conv-stack file of edgeml_amd.convnet as kind "convnet" (net: a tapnet.TapNet whose
     ConvSpec is rebuilt from the tensor shapes, for the SSDLite stage-N map of (num_classes, reduced_tail) pooled
     to resize x resize; pools: the net's pools when not the convnet CLI's default).  ValueError when the first conv
     layer's Cin is not the stage's channel count, when the first linear width is not the pooled geometry's, and
@@ -140,6 +232,8 @@ def load_estimator(path, width, support=False, stage=None, resize=None, pools=No
     shapes, and when the model's feature width is not `width`."""
     from . import gbr, kpredict, rfr
     from .estimator import MlpSpec
+    if baseline is not None:
+        return load_baseline(path, width, baseline)
     if str(path).endswith(".pth"):
         named = torch.load(path, map_location="cpu", weights_only=True)
         named = {k: v.numpy() for k, v in named.items() if torch.is_tensor(v)}
@@ -177,7 +271,9 @@ def load_estimator(path, width, support=False, stage=None, resize=None, pools=No
     with open(path, "rb") as f:
         m = pickle.load(f)
     if not isinstance(m, dict) or "mean" not in m or "scale" not in m:
-        raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir")
+        hint = " (an Adaptive Feeding file of edgeml_amd.baseline: give --baseline af)" if _is_af_file(m) else \
+            " (a DCSB file of edgeml_amd.baseline: give --baseline dcsb)" if _is_dcsb_file(m) else ""
+        raise ValueError(f"{path}: not a wts<fold>.pickle of edgeml_amd.estimator --model-dir{hint}")
     if stage is not None:
         raise ValueError(f"{path}: --stage {stage} takes a conv-stack wts<fold>.pth of edgeml_amd.convnet; this "
                          "estimator reads the stage-24 output features (drop --stage and --resize)")
@@ -311,7 +407,8 @@ def gather(pairs, out=None, stream=None):
 class Chain:
     """The run_batches post hook of the weak model: rows -> features -> estimate -> flags -> pack on the
     slot's stream.  Its device scratch and pinned result buffers live on the slot; the packed images are
-    a fresh tensor per batch, handed on to the strong stage."""
+    a fresh tensor per batch, handed on to the strong stage.  The "dcsb" baseline decides on the rows
+    (rows -> edgedet_offload_dcsb -> pack: no features); "af" is rows -> features -> edgedet_offload_svm -> pack."""
 
     def __init__(self, estimator, threshold, num_class, k, dataset):
         self.est, self.threshold, self.num_class, self.k, self.dataset = estimator, float(threshold), num_class, k, dataset
@@ -375,11 +472,20 @@ class Chain:
             buf = sl["offload"] = {
                 "key": (B, K, D, wb), "kws": d((wb,), torch.uint8) if wb else None,
                 "rows": d((B, K, 6), torch.float64), "nrow": d((B,), torch.int32),
-                "feat": d((B, D), torch.float64), "x32": d((B, D), torch.float32), "est32": d((B,), torch.float32),
+                "feat": None, "x32": None, "est32": None,
                 "est": d((B,), torch.float64), "flag": d((B,), torch.uint8), "count": d((1,), torch.int32),
                 "index": d((B,), torch.int32),
                 "h_est": p((B,), torch.float64), "h_flag": p((B,), torch.uint8), "h_count": p((1,), torch.int32),
                 "h_index": p((B,), torch.int32)}
+        # what the rule reads, made when a rule first needs it (the slot may have served another estimator under
+        # the same key): dcsb decides on the rows alone, af needs the features but not the MLP's float32 scratch
+        kind = self.est.kind
+        need = [] if kind == "dcsb" else [("feat", (B, D), torch.float64)]
+        if kind not in CLASSIFIER_KINDS:
+            need += [("x32", (B, D), torch.float32), ("est32", (B,), torch.float32)]
+        for name, shape, dt in need:
+            if buf[name] is None:
+                buf[name] = torch.zeros(shape, dtype=dt, device=plan.device)
         return buf
 
     def __call__(self, plan, sl, stream, tag):
@@ -392,8 +498,11 @@ class Chain:
             b = self.buffers(plan, sl)
             format_rows(plan.out_count.tensor(), plan.out_box.tensor(), plan.out_score.tensor(),
                         plan.out_label.tensor(), plan.H, plan.W, self.dataset, b["rows"], b["nrow"], stream)
-            row_features(b["rows"], b["nrow"], self.num_class, self.k, b["feat"], stream)
-            self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"], b["kws"]), stream)
+            if self.est.kind == "dcsb":  # no features: the rule reads the rows
+                self.est.decide(None, self.threshold, b["est"], b["flag"], stream=stream, rows=b["rows"], nrow=b["nrow"])
+            else:
+                row_features(b["rows"], b["nrow"], self.num_class, self.k, b["feat"], stream)
+                self.est.decide(b["feat"], self.threshold, b["est"], b["flag"], (b["x32"], b["est32"], b["kws"]), stream)
         images = plan.input.tensor()
         packed = torch.empty_like(images)  # this batch's own: it outlives the slot's next use
         pack(b["flag"], images, packed, b["count"], b["index"], stream)
@@ -405,8 +514,10 @@ class Chain:
 
 # ---------------------------------------------------------------------------------------- the cascade
 def run(img_dir, estimator, threshold, k=25, dataset="coco", weak="ssd", strong="faster_rcnn", weak_path="",
-        strong_path="", weak_batch=0, strong_batch=0, decode="gpu", on_rows=None, device="cuda:0"):
-    """Run the cascade on a directory of images.  estimator: an Estimator or a wts file; weak / strong:
+        strong_path="", weak_batch=0, strong_batch=0, decode="gpu", on_rows=None, device="cuda:0", baseline=None):
+    """Run the cascade on a directory of images.  estimator: an Estimator or a wts file (baseline "af" / "dcsb":
+    a saved model of edgeml_amd.baseline; such a classifier takes threshold 0.0, anything else is a ValueError:
+    estimate is then the SVM's decision value, or DCSB's 0.0 / 1.0); weak / strong:
     a detect CLI model name (loaded from weak_path / strong_path) or a detector of models.py.  Returns
     {names, estimate [n] float64, offloaded [n] bool, threshold, ratio_realized, rows {name: final
     rows}, weak_rows {name: weak rows}, strong_batches [[name, ...], ...], seconds {phase: host
@@ -415,13 +526,17 @@ def run(img_dir, estimator, threshold, k=25, dataset="coco", weak="ssd", strong=
     import time
     from . import detect, distributed as dist_mod
     clock = {"start": time.perf_counter(), "strong_model": 0.0}
+    if isinstance(estimator, Estimator) and estimator.kind in CLASSIFIER_KINDS:
+        _classifier_threshold(estimator.kind, threshold)
     if not torch.cuda.is_available():
         raise RuntimeError("edgeml_amd.offload needs an MI355X (HIP) device; there is no CPU path")
     num_class = 20 if dataset == "voc" else 80      # classes of the .npy rows (features.main)
     det_classes = 91 if dataset == "coco" else 21   # classes of the detectors (detect.main)
     if not isinstance(estimator, Estimator):
-        estimator = load_estimator(estimator, num_class + 5 * k, support=True)
-    if estimator.kind != "convnet" and estimator.width != num_class + 5 * k:
+        estimator = load_estimator(estimator, num_class + 5 * k, support=True, baseline=baseline)
+    if estimator.kind in CLASSIFIER_KINDS:
+        _classifier_threshold(estimator.kind, threshold)
+    if estimator.kind not in ("convnet", "dcsb") and estimator.width != num_class + 5 * k:
         raise ValueError(f"the estimator takes {estimator.width} features, the cascade makes {num_class + 5 * k}")
     torch.cuda.set_device(device)
     data = detect.ObjectDetectionDataset(img_dir)
@@ -511,16 +626,19 @@ def main(opts):
     if opts.stage is not None and opts.weak != "ssd":
         raise SystemExit("edgeml_amd.offload: --stage reads SSDLite's stage table; --weak ssd is the only producer")
     try:
-        if opts.stage is None and str(opts.estimator).endswith(".pth") and _has_conv_stacks(opts.estimator):
-            raise ValueError(f"{opts.estimator}: a conv-stack estimator of edgeml_amd.convnet: give --stage N (the "
-                             "SSDLite stage it was trained on) and --resize S (its --resize)")
-        estimator = load_estimator(opts.estimator, num_class + 5 * opts.k, support=True, stage=opts.stage,
-                                   resize=opts.resize, pools=opts.pools,
-                                   num_classes=91 if opts.dataset == "coco" else 21,
-                                   reduced_tail=_weak_tail(opts), fused=True if opts.fused else None)
+        if opts.baseline:
+            estimator = load_baseline(opts.estimator, num_class + 5 * opts.k, opts.baseline)
+        else:
+            if opts.stage is None and str(opts.estimator).endswith(".pth") and _has_conv_stacks(opts.estimator):
+                raise ValueError(f"{opts.estimator}: a conv-stack estimator of edgeml_amd.convnet: give --stage N (the "
+                                 "SSDLite stage it was trained on) and --resize S (its --resize)")
+            estimator = load_estimator(opts.estimator, num_class + 5 * opts.k, support=True, stage=opts.stage,
+                                       resize=opts.resize, pools=opts.pools,
+                                       num_classes=91 if opts.dataset == "coco" else 21,
+                                       reduced_tail=_weak_tail(opts), fused=True if opts.fused else None)
     except ValueError as e:
         raise SystemExit(f"edgeml_amd.offload: {e}") from None
-    threshold = resolve_threshold(opts)
+    threshold = 0.0 if opts.baseline else resolve_threshold(opts)  # a classifier: offload where the class is 1
     Path(opts.save_dir).mkdir(parents=True, exist_ok=True)
     if opts.weak_dir:
         Path(opts.weak_dir).mkdir(parents=True, exist_ok=True)
@@ -573,7 +691,19 @@ def getargs(argv=None):
     a.add_argument("--pools", type=int, nargs="*", default=None, help="The net's --pools when not the default 1 1 0 ...")
     a.add_argument("--fused", action="store_true", help="Run the conv-stack estimator as one fused launch "
                    "(csrc/tapnet.hip) instead of the layered eval forward.")
+    a.add_argument("--baseline", choices=CLASSIFIER_KINDS, default=None, help="--estimator is a saved comparison "
+                   "baseline of edgeml_amd.baseline --model_dir (af: the Adaptive Feeding SVM, dcsb: the DCSB rule): a "
+                   "classifier, offloading where its class is 1; replaces --threshold / --ratio.")
     opts = a.parse_args(argv)
+    if opts.baseline:
+        given = {"--ratio": opts.ratio is not None, "--estimates": opts.estimates is not None,
+                 "--threshold": opts.threshold is not None, "--stage": opts.stage is not None,
+                 "--resize": opts.resize is not None, "--pools": opts.pools is not None, "--fused": opts.fused}
+        for flag, on in given.items():
+            if on:
+                raise SystemExit(f"edgeml_amd.offload: --baseline {opts.baseline}: a classifier has no ratio (it "
+                                 f"offloads where its class is 1, on the weak detector's output): drop {flag}")
+        return opts
     if (opts.threshold is None) == (opts.ratio is None):
         a.error("give either --threshold T or --ratio R with --estimates EST_DIR")
     if opts.ratio is not None and (opts.estimates is None or not 0.0 <= opts.ratio <= 1.0):

@@ -65,7 +65,7 @@ EXPORTS = ("edgedet_plan_run", "edgedet_graph_create", "edgedet_graph_launch", "
            "edgedet_svr_workspace_size", "edgedet_svr_kernel_matrix", "edgedet_svr_fit", "edgedet_svr_predict",
            "edgedet_lsvr_fit",
            "edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide", "edgedet_offload_pack",
-           "edgedet_offload_gather", "edgedet_offload_flag",
+           "edgedet_offload_gather", "edgedet_offload_flag", "edgedet_offload_dcsb", "edgedet_offload_svm",
            "edgedet_kmodel_prepare", "edgedet_kmodel_workspace_size", "edgedet_svr_model_predict",
            "edgedet_knn_model_predict",
            "edgedet_gbr_workspace_size", "edgedet_gbr_prepare", "edgedet_gbr_fit", "edgedet_gbr_model_predict",
@@ -210,6 +210,8 @@ def lib():
     L.edgedet_offload_pack.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]
     L.edgedet_offload_gather.argtypes = [_vp, _vp, _i32, _i64, _vp, _vp]
     L.edgedet_offload_flag.argtypes = [_vp, _i64, _dbl, _vp, _vp]
+    L.edgedet_offload_dcsb.argtypes = [_vp, _vp, _i64, _i64, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.edgedet_offload_svm.argtypes = [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]
     L.edgedet_kmodel_prepare.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
     L.edgedet_kmodel_workspace_size.argtypes = [_i64, _i64, _i64, _i32]
     L.edgedet_kmodel_workspace_size.restype = _i64
@@ -218,7 +220,8 @@ def lib():
     L.edgedet_knn_model_predict.argtypes = [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp,
                                             _vp]
     for name in ("edgedet_offload_rows", "edgedet_offload_features", "edgedet_offload_decide",
-                 "edgedet_offload_pack", "edgedet_offload_gather", "edgedet_offload_flag", "edgedet_kmodel_prepare",
+                 "edgedet_offload_pack", "edgedet_offload_gather", "edgedet_offload_flag", "edgedet_offload_dcsb",
+                 "edgedet_offload_svm", "edgedet_kmodel_prepare",
                  "edgedet_svr_model_predict", "edgedet_knn_model_predict"):
         getattr(L, name).restype = ctypes.c_int
     L.edgedet_gbr_workspace_size.argtypes = [_vp, _i32, _i64]

@@ -696,6 +696,31 @@ int edgedet_offload_decide(const double* feat, int64_t B, int64_t D, const doubl
 /* flag [B] = est [B] > threshold (strict, float64): edgedet_offload_decide's last step on estimates another
  * call wrote (edgedet_svr_model_predict, edgedet_knn_model_predict); the same kernel, est is only read. */
 int edgedet_offload_flag(const double* est, int64_t B, double threshold, uint8_t* flag, void* stream);
+/*
+ * The DCSB baseline's decision (baseline.py:129-141) for one fitted model (conf_thresh, num_thresh, area_thresh)
+ * on the padded rows of edgedet_offload_rows.  Per image b, over its first clamp(nrow[b], 0, K) rows r:
+ * conf = r[5]; x1 = r[1] - r[3]/2, y1 = r[2] - r[4]/2, x2 = r[1] + r[3]/2, y2 = r[2] + r[4]/2 and
+ * area = (x2 - x1) * (y2 - y1) (xywh2xyxy then get_area, each op rounded on its own);
+ * est_num = #(conf > conf_thresh), det_num = #(conf > 0.5), min_area = the minimum area among the rows with
+ * conf > conf_thresh (0.0 when there are none; a NaN area wins, as np.amin);
+ * cls = est_num != det_num && (est_num > num_thresh || min_area < area_thresh); est[b] = cls ? 1.0 : 0.0 and
+ * flag[b] = cls.  Every comparison is strict and the rows at or past nrow[b] are never read.  est_num, det_num
+ * and min_area [B] are optional (null: not written).  float64 and integers only; one wave per image, nothing
+ * allocated.  B <= 65535 (B == 0: no launch), 1 <= K < 2^24.
+ */
+int edgedet_offload_dcsb(const double* rows, const int32_t* nrow, int64_t B, int64_t K, double conf_thresh,
+                         int32_t num_thresh, double area_thresh, int32_t* est_num, int32_t* det_num,
+                         double* min_area, double* est, uint8_t* flag, void* stream);
+/*
+ * The Adaptive Feeding baseline's decision on feat [B][D] (edgedet_offload_features' output): v [Dp] is the
+ * SVM's coef [D], its intercept at index D, then zeros, Dp = (D + 1 + 15) / 16 * 16 <= 256 (anything else is
+ * refused): baseline.pad_features' layout with the padding implied, no padded copy of the features is read.
+ * est[b] is, bit for bit, what edgedet_svm_decision gives for row b of pad_features(feat) with that v (sixteen
+ * lanes per row, a lane's terms in increasing k, then the 8-4-2-1 butterfly); flag[b] = est[b] > 0 (strict).
+ * B <= 65535 (B == 0: no launch).
+ */
+int edgedet_offload_svm(const double* feat, int64_t B, int64_t D, const double* v, int64_t Dp, double* est,
+                        uint8_t* flag, void* stream);
 /* The images b of src [B][image_bytes] with flag[b] != 0 copied to the front of dst in index order
  * (flags read on the device); *count their number, index[0 .. count) their source indices.  16-byte
  * copies where an image's two ends are 16-byte aligned, bytes otherwise and for the tail.  Nothing is
