@@ -7,6 +7,10 @@
 * dropout on (p = 0.1, another random stream): both fits learn the same function to a similar
   validation loss;
 * the CLI writes regression.py's estimate files.
+
+These are trajectory comparisons.  The kernel-level reference is tests/mlp_ref.py: tests/test_gpu_mlp_exact.py holds
+mlp_fit_kernel and mlp_predict_kernel to its float32 restatement bit for bit, dropout on included, and
+tests/test_mlp_ref_host.py anchors that restatement to torch float64 autograd.
 """
 import os
 import tempfile
